@@ -25,11 +25,19 @@ Per step the shard histograms and list lengths are combined with one RCCL
 all-reduce (overlapped with the next step's compute) and the near-miss / nice
 lists are all-gathered when non-empty, so every rank ends holding the whole
 field's results -- the north star's exchange, inside the timed region.  Under
-strong scaling rank 0 then times the whole field alone on its GPU (the other
-ranks wait) and reports strong_efficiency = T1 / (N * T_N) from the same run.
+strong scaling with --full rank 0 then times the whole field alone on its GPU (the
+other ranks wait) and reports strong_efficiency = T1 / (N * T_N) from the same run.
 Timing: barrier + device sync on both sides of exactly K steps, max over ranks.
 
-    python bench.py [--gpus N --steps K --warmup W] [--no-cpu-baseline]
+A plain run sets up, warms up, times the K steps and prints the result line.
+`--full` adds what takes runs of its own or compares with a reference: each
+mode alone over the same field, the detailed kernel launched alone (roofline),
+T1 of a strong-scaling run, the last field against the oracle fixture, and the
+CPU baseline.  `--dump-outputs DIR` writes the last timed field's results as
+DIR/<name>.npy (float64; see dump_outputs).
+
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline]]
 """
 from __future__ import annotations
 
@@ -82,7 +90,14 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=10)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure each mode alone, the detailed kernel alone (roofline), T1 of a "
+                        "strong-scaling run and the CPU baseline, and check the last field against "
+                        "the oracle fixture")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed field's results to DIR/<name>.npy (float64)")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="--full: leave the CPU baseline out")
     p.add_argument("--cpu-seconds", type=float, default=15.0,
                    help="target CPU work for the bounded cpu_baseline sample")
     p.add_argument("--mode", choices=["both", "detailed", "niceonly"], default="both")
@@ -296,6 +311,33 @@ def fixture_check(field, base, mode, res, world=1):
     return out
 
 
+def dump_outputs(out_dir, field, res):
+    """The last timed field's results -- what a caller of the timed path gets
+    back for it -- as float64 arrays (every value is an integer below 2^53, so
+    exact).  Numbers are u128: they are stored as offsets from the field's
+    start.  The two lists are stored with their length in front, so no array is
+    empty.
+      detailed_distribution.npy  count of n per num_uniques 1..base
+      detailed_near_misses.npy   [len, (n - start, num_uniques) per near miss ...]
+      niceonly_nice_numbers.npy  [len, n - start per nice number ...]
+      niceonly_stats.npy         [MSD ranges, numbers in them, stride candidates]
+    A mode that did not run writes no file."""
+    import numpy as np
+    _, det, nic, st = res
+    os.makedirs(out_dir, exist_ok=True)
+    s = field.range_start
+
+    def save(name, values):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(values, dtype=np.float64))
+    if det is not None:
+        save("detailed_distribution", [d.count for d in det.distribution])
+        near = [v for n in det.nice_numbers for v in (n.number - s, n.num_uniques)]
+        save("detailed_near_misses", [len(det.nice_numbers)] + near)
+    if nic is not None and st is not None:
+        save("niceonly_nice_numbers", [len(nic.nice_numbers)] + [n.number - s for n in nic.nice_numbers])
+        save("niceonly_stats", [st.ranges, st.range_numbers, st.candidates])
+
+
 def main(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -372,7 +414,8 @@ def main(args):
             det_ctx.synchronize()
 
     last_stats = [None]
-    last_res = [None]  # the last field's whole results (fixture_check after the timed region)
+    last_res = [None]  # the last field's whole results (fixture_check, --dump-outputs)
+    last_raw = [None]  # the same of the synchronous calls at N = 1, as they return them
     checked = [0]  # fields whose whole-field results came back and were checked
 
     def check(res):
@@ -397,13 +440,14 @@ def main(args):
 
         def step():
             if dist is None:
-                (hist, _), (_, st) = runner.both_raw(
+                (hist, near), (nice, st) = runner.both_raw(
                     (field.range_start, field.range_end) if modes[0] else None,
                     (field.range_start, field.range_end) if modes[1] else None, base, **nice_opts)
                 kern.append(det_ctx.kernel_stats().kernel_ms)
                 if modes[0]:
                     assert sum(hist) == job_size
                 last_stats[0] = st or last_stats[0]
+                last_raw[0] = (hist, near, nice, st)
             else:
                 done = D.process_field_both_pipelined(ex, field, base, runner, **nice_opts)
                 kern.append(det_ctx.kernel_stats().kernel_ms)
@@ -437,8 +481,16 @@ def main(args):
     checked[0] = 0
     elapsed = timed(step, args.steps, barrier_sync, dist, tail=tail)
     fields_checked = checked[0]  # every field of the timed region came back whole and was checked
-    # the timed region's last field against the oracle fixture of this field
-    fixture = fixture_check(field, base, args.mode, last_res[0], world) if last_res[0] is not None else None
+    if last_raw[0] is not None:
+        hist, near, nice, st = last_raw[0]
+        last_res[0] = (field, D._results(hist, near, base) if modes[0] else None,
+                       N.FieldResults(distribution=[], nice_numbers=[N.NiceNumberSimple(n, base) for n in nice])
+                       if modes[1] else None, st)
+    if args.dump_outputs and rank == 0 and last_res[0] is not None:
+        dump_outputs(args.dump_outputs, field, last_res[0])
+    # --full: the timed region's last field against the oracle fixture of this field
+    fixture = (fixture_check(field, base, args.mode, last_res[0], world)
+               if args.full and last_res[0] is not None else None)
     # Event spans of the detailed launches inside the timed region: consecutive
     # fields run on different slots' streams and overlap at their edges by
     # design (a field's first workgroups fill the CUs the previous field's last
@@ -449,7 +501,7 @@ def main(args):
     # Each mode alone over the same field, same pipeline, same timing rules
     # (BOTH modes check every n of the field; these are the per-mode rates).
     per_mode = {}
-    if args.mode == "both" and not args.sync:
+    if args.full and args.mode == "both" and not args.sync:
         for name, sel in (("detailed", (True, False)), ("niceonly", (False, True))):
             p1 = D.FieldPipeline(det_ctx if sel[0] else _Skip(), nice_ctx if sel[1] else _Skip(),
                                  dist, group=ex_group, exchange=shm_ex, depth=args.depth,
@@ -474,7 +526,7 @@ def main(args):
     # events on the launch stream; the same dispatches are the last fd2 ones in
     # a rocprofv3 kernel trace of this command (scripts/trace_summary.py).
     iso_ms = []
-    if modes[0]:
+    if args.full and modes[0]:
         s_r, e_r = D.shard_bounds(field.range_start, field.range_end, rank, world)
         for _ in range(max(3, min(10, args.steps))):
             hist, _ = det_ctx.detailed_raw(s_r, e_r, base)
@@ -484,7 +536,7 @@ def main(args):
 
     # Strong scaling: the whole field on rank 0's GPU alone, same run (T1).
     t1 = None
-    if dist is not None and strong and world > 1:
+    if args.full and dist is not None and strong and world > 1:
         if rank == 0:
             solo = make_pipeline(None)
 
@@ -549,13 +601,15 @@ def main(args):
             "pipeline_depth": None if args.sync else args.depth,
             "exchange_lag": args.exchange_lag if dist is not None else None,
             "exchange_backend": ex_kind,
+            "full": args.full,
             "probe_lib": PROBE_LIB,
             "gpu_max_hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
             "gpu_max_hw_queues_exported": HW_QUEUES_EXPORTED,
         },
     }
     line["fields_checked"] = fields_checked
-    line["verified_against_fixture"] = bool(fixture and fixture["verified"])
+    if args.full:
+        line["verified_against_fixture"] = bool(fixture and fixture["verified"])
     if fixture is not None:
         line["fixture_check"] = fixture
     for name, el in per_mode.items():
@@ -628,7 +682,7 @@ def main(args):
         line["niceonly"] = {"ranges": st.ranges, "range_numbers": st.range_numbers,
                             "candidates": st.candidates, "launches": st.launches,
                             "rank0_dealt_chunks": f"every {world}-th" if world > 1 else "all"}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(br.range_start, args.cpu_seconds, base, field_size)
     print(json.dumps(line), file=json_out, flush=True)
     if args.sync:

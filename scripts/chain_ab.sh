@@ -14,7 +14,7 @@ out=gpurun_out/chain.log
 for pass in 1 2; do
   for c in 0 700 850 950; do
     for fs in 1.25e8 2.5e8 1e9; do
-      NICE_FD2_CHAIN=$c timeout -k 10 120 python3 bench.py --probe-lib --field-size $fs --steps 100 --warmup 20 \
+      NICE_FD2_CHAIN=$c timeout -k 10 120 python3 bench.py --probe-lib --field-size $fs --steps 100 --warmup 20 --full \
           --no-cpu-baseline > gpurun_out/ch.json 2> gpurun_out/ch.err
       python3 -c "import json; d=json.loads(open('gpurun_out/ch.json').readline()); print('chain', $c, '$fs', round(d['ms_per_step'],4), round(d['detailed_ms_per_step'],4), d['verified_against_fixture'])" >> $out
     done

@@ -3,6 +3,8 @@
 #   bash scripts/gpu.sh bench TAG [bench args]     # one bench line -> gpurun_out/bench_TAG.json
 #   bash scripts/gpu.sh torchrun N TAG [args]      # bench under torchrun, N ranks on device(s)
 #   bash scripts/gpu.sh prof TAG [bench args]      # rocprofv3 kernel trace + stats of that bench
+#                                                  # (--full among the args: the isolated launches
+#                                                  # and roofline figures trace_summary.py reads)
 #   bash scripts/gpu.sh pmc TAG "COUNTERS" [bench args]   # one rocprofv3 --pmc pass of that bench
 #   bash scripts/gpu.sh configs                    # every BASELINE config on one GPU
 #   bash scripts/gpu.sh massive                    # whole massive field, dealt 8 ways

@@ -10,7 +10,7 @@ out=gpurun_out/msd_wg.log
 for pass in 1 2; do
   for wg in 256 64; do
     for fs in 1.25e8 1e9; do
-      NICE_MSD_WG=$wg timeout -k 10 120 python3 bench.py --probe-lib --field-size $fs --steps 100 --warmup 20 \
+      NICE_MSD_WG=$wg timeout -k 10 120 python3 bench.py --probe-lib --field-size $fs --steps 100 --warmup 20 --full \
           --no-cpu-baseline > gpurun_out/mw.json 2> gpurun_out/mw.err
       python3 -c "import json; d=json.loads(open('gpurun_out/mw.json').readline()); print($wg, '$fs', round(d['ms_per_step'],4), round(d['detailed_ms_per_step'],4), round(d['niceonly_ms_per_step'],4))" >> $out
     done

@@ -1,5 +1,6 @@
 """Dominant-kernel figures from a rocprofv3 --kernel-trace CSV of bench.py
-(scripts/gpu.sh prof TAG), next to the bench line the same command printed:
+--full (scripts/gpu.sh prof TAG --full), next to the bench line the same command
+printed:
 
     python scripts/trace_summary.py --isolated 10 --bench gpurun_out/prof_TAG.json \
         gpurun_out/prof_TAG/**/*kernel_trace.csv > profiles/r03/bench_trace_summary.json

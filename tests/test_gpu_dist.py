@@ -101,7 +101,7 @@ def test_bench_two_ranks_strong_scaling_branch(launcher, exchange):
     import subprocess
     import sys
     args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-            "--no-cpu-baseline", "--dist-backend", "gloo", "--exchange-backend", exchange]
+            "--full", "--no-cpu-baseline", "--dist-backend", "gloo", "--exchange-backend", exchange]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port())] + args
