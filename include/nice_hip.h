@@ -269,6 +269,12 @@ uint64_t nice_processing_chunk_size(void);
 int nice_gpu_supports_base(uint32_t base);
 /* 1 if detailed fields of this base inside its range use the FD kernel. */
 int nice_fd_kernel_base(uint32_t base);
+/* 1 if niceonly fields of this base inside its range use the compile-time
+ * niceonly kernels (in-range limb paths, square-survivor queue: square_ok is
+ * counted): every base with an FD kernel whose k = 2 stride table has a
+ * residue -- 40 42 44 45 48 49 50 52 53 54 57 58 60 62 64 65 68 80.  Every
+ * other base runs the run-time-base kernels (square_ok stays 0). */
+int nice_niceonly_fast_base(uint32_t base);
 
 /* Host MSD filter, get_valid_ranges_recursive (msd_prefix_filter.rs:583-674)
  * with max depth 22 and factor 2: writes (start_lo, start_hi, end_lo, end_hi)
@@ -284,8 +290,9 @@ int nice_stride_table(uint32_t base, uint32_t k, uint64_t *modulus, uint32_t *re
                       size_t cap, size_t *n_out);
 
 /* Test hooks (no device needed): the in-range fast paths of the niceonly
- * kernels (radix_fast.hpp) evaluated on the host, bases 40/50/52/53/54/80 with n (and
- * [start, end)) inside the base's valid range.  is_nice: 1/0 like get_is_nice
+ * kernels (radix_fast.hpp) evaluated on the host, for the bases of
+ * nice_niceonly_fast_base with n (and [start, end)) inside the base's valid
+ * range.  is_nice: 1/0 like get_is_nice
  * (client_process.rs:222-253); msd: 1/0 like has_duplicate_msd_prefix on
  * [start, end - 1] (msd_prefix_filter.rs:382-563); unique: the unique-digit
  * count of n^2 and n^3 by the same limb path (get_num_unique_digits,
@@ -304,7 +311,7 @@ int nice_debug_unique_counts(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t co
                              uint32_t base, uint32_t *out);
 int nice_debug_is_nice(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t count, uint32_t base,
                        uint32_t *out);
-/* The niceonly kernel's in-range limb path (bases 40/50/52/53/54/80, every n
+/* The niceonly kernel's in-range limb path (nice_niceonly_fast_base bases, every n
  * inside the base's valid range, else NICE_ERR_INVALID): the unique-digit
  * count its niceness test compares with the base. */
 int nice_debug_unique_fast(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t count, uint32_t base,

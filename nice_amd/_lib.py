@@ -30,7 +30,7 @@ EXPORTS = (
     "nice_process_range_detailed", "nice_process_range_niceonly",
     "nice_process_range_niceonly_ex", "nice_last_kernel_stats", "nice_base_range",
     "nice_near_miss_cutoff", "nice_gpu_batch_size", "nice_processing_chunk_size",
-    "nice_gpu_supports_base", "nice_fd_kernel_base", "nice_msd_valid_ranges",
+    "nice_gpu_supports_base", "nice_fd_kernel_base", "nice_niceonly_fast_base", "nice_msd_valid_ranges",
     "nice_msd_skippable", "nice_stride_table", "nice_debug_unique_counts",
     "nice_debug_is_nice", "nice_debug_unique_fast", "nice_check_is_nice_inrange", "nice_check_unique_inrange", "nice_check_msd_skippable_inrange",
     "nice_fd_segment_cuts", "nice_validate_detailed", "nice_detailed_submit",
@@ -122,6 +122,7 @@ def lib():
         "nice_processing_chunk_size": ([], u64),
         "nice_gpu_supports_base": ([u32], i32),
         "nice_fd_kernel_base": ([u32], i32),
+        "nice_niceonly_fast_base": ([u32], i32),
         "nice_msd_valid_ranges": ([u64, u64, u64, u64, u32, u64, P64, sz, PSZ], i32),
         "nice_msd_skippable": ([u64, u64, u64, u64, u32], i32),
         "nice_stride_table": ([u32, u32, P64, P32, sz, PSZ], i32),

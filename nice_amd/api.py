@@ -61,6 +61,13 @@ def gpu_supports_base(base: int) -> bool:
     return bool(lib().nice_gpu_supports_base(base))
 
 
+def niceonly_fast_base(base: int) -> bool:
+    """The base's niceonly fields inside its range run the compile-time kernels
+    (square-survivor queue, `NiceonlyStats.square_ok` counted): every base with
+    an FD kernel and a non-empty k = 2 stride table."""
+    return bool(lib().nice_niceonly_fast_base(base))
+
+
 @dataclass
 class StrideTable:
     """StrideTable (common/src/stride_filter.rs:20-87), host-built by the library."""

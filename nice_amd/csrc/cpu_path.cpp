@@ -22,6 +22,7 @@
 
 #include "../../include/nice_hip.h"
 #include "host_math.hpp"
+#include "niceonly_bases.h"
 
 namespace {
 
@@ -178,17 +179,15 @@ int niceonly_cpu(u128 s, u128 e, const BP &bp, uint32_t k, int threads, nice_num
     return NICE_OK;
 }
 
-// Compile-time divisors for the benchmark and live bases, run-time otherwise.
+// Compile-time divisors for b10 and the niceonly fast bases
+// (niceonly_bases.h), run-time otherwise.
 template <class F>
 int with_base(uint32_t base, F &&f) {
     switch (base) {
     case 10: return f(nice::CtBase<10>{});
-    case 40: return f(nice::CtBase<40>{});
-    case 50: return f(nice::CtBase<50>{});
-    case 52: return f(nice::CtBase<52>{});
-    case 53: return f(nice::CtBase<53>{});
-    case 54: return f(nice::CtBase<54>{});
-    case 80: return f(nice::CtBase<80>{});
+#define X(b) case b: return f(nice::CtBase<b>{});
+        NICE_NICEONLY_BASES(X)
+#undef X
     default: return f(nice::RtBase(base));
     }
 }

@@ -16,6 +16,8 @@
 #include <utility>
 #include <vector>
 
+#include "niceonly_bases.h"
+
 namespace nice {
 
 typedef unsigned __int128 u128;
@@ -386,8 +388,9 @@ struct MsdFilterT {
     }
 };
 
-// Runtime-dispatched MSD producer: compile-time bases for the benchmark /
-// production bases, a runtime-divisor instance for everything else.
+// Runtime-dispatched MSD producer: compile-time divisors for the niceonly
+// fast bases (niceonly_bases.h), a runtime-divisor instance for everything
+// else.
 struct MsdRunner {
     virtual ~MsdRunner() {}
     virtual bool skippable(u128 s, u128 e) const = 0;
@@ -406,9 +409,9 @@ struct MsdRunnerT : MsdRunner {
 };
 inline std::unique_ptr<MsdRunner> make_msd(uint32_t base) {
     switch (base) {
-    case 40: return std::unique_ptr<MsdRunner>(new MsdRunnerT<CtBase<40>>(CtBase<40>{}));
-    case 50: return std::unique_ptr<MsdRunner>(new MsdRunnerT<CtBase<50>>(CtBase<50>{}));
-    case 80: return std::unique_ptr<MsdRunner>(new MsdRunnerT<CtBase<80>>(CtBase<80>{}));
+#define X(b) case b: return std::unique_ptr<MsdRunner>(new MsdRunnerT<CtBase<b>>(CtBase<b>{}));
+        NICE_NICEONLY_BASES(X)
+#undef X
     default: return std::unique_ptr<MsdRunner>(new MsdRunnerT<RtBase>(RtBase(base)));
     }
 }

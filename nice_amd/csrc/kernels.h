@@ -1,5 +1,6 @@
 // kernels.h -- host-side launch entry points for the gfx950 kernels
-// (implemented in detailed.hip / niceonly.hip, used by nice_abi.cpp).
+// (implemented in detailed.hip / niceonly.hip / niceonly_part.hip, used by
+// nice_abi.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -104,7 +105,6 @@ struct NiceonlyLaunch {
     NumOut out;
     NiceFinish fin;
 };
-bool niceonly_specialised(uint32_t base);
 hipError_t launch_niceonly(const NiceonlyLaunch &p, int num_cus, hipStream_t s);
 
 // Device MSD filter (msd_prefix_filter.rs:583-658 as a level-synchronous BFS):
@@ -183,7 +183,7 @@ hipError_t launch_unique_counts(const uint64_t *n_pairs, uint32_t count, uint32_
                                 uint32_t *out, hipStream_t s);
 hipError_t launch_is_nice(const uint64_t *n_pairs, uint32_t count, uint32_t base,
                           uint32_t *out, hipStream_t s);
-// In-range n of a niceonly fast base (40/50/52/53/54/80): the unique-digit
+// In-range n of a niceonly fast base (niceonly_bases.h): the unique-digit
 // count by niceonly_kernel's limb path (radix_fast.hpp unique_fast).
 hipError_t launch_unique_fast(const uint64_t *n_pairs, uint32_t count, uint32_t base,
                               uint32_t *out, hipStream_t s);

@@ -32,6 +32,7 @@
 #include "../../include/nice_hip.h"
 #include "host_math.hpp"
 #include "kernels.h"
+#include "niceonly_bases.h"
 #include "probe.hpp"
 #include "radix_fast.hpp"
 
@@ -1145,17 +1146,11 @@ int nice_debug_is_nice(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t count, u
     return NICE_OK;
 }
 
-// The bases with niceonly fast paths (niceonly.hip NICE_NICEONLY_BASES).
-#define NICE_FAST_BASES(X) X(40) X(50) X(52) X(53) X(54) X(80)
-static bool nice_fast_base(uint32_t base) {
-    switch (base) {
-#define X(b) case b:
-        NICE_FAST_BASES(X)
-#undef X
-        return true;
-    default: return false;
-    }
-}
+// The bases with niceonly fast paths (niceonly_bases.h, the one list).
+#define NICE_FAST_BASES(X) NICE_NICEONLY_BASES(X)
+static bool nice_fast_base(uint32_t base) { return nice::niceonly_fast_base(base); }
+
+int nice_niceonly_fast_base(uint32_t base) { return nice_fast_base(base) ? 1 : 0; }
 
 int nice_debug_unique_fast(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t count, uint32_t base,
                            uint32_t *out) {
@@ -1186,7 +1181,7 @@ int nice_check_is_nice_inrange(uint32_t base, uint64_t lo, uint64_t hi) {
     u128 rs, re;
     const u128 n = mk(lo, hi);
     if (!nice_fast_base(base) || nice::base_range_cached(base, rs, re) != 1 || n < rs || n >= re)
-        return fail(NICE_ERR_INVALID, "n outside the base's valid range (or base not 40/50/80)");
+        return fail(NICE_ERR_INVALID, "n outside the base's valid range (or base without a niceonly fast path)");
     switch (base) {
 #define X(b) case b: return nice::is_nice_fast<b>(lo, hi) ? 1 : 0;
         NICE_FAST_BASES(X)
@@ -1199,7 +1194,7 @@ int nice_check_unique_inrange(uint32_t base, uint64_t lo, uint64_t hi) {
     u128 rs, re;
     const u128 n = mk(lo, hi);
     if (!nice_fast_base(base) || nice::base_range_cached(base, rs, re) != 1 || n < rs || n >= re)
-        return fail(NICE_ERR_INVALID, "n outside the base's valid range (or base not 40/50/52/53/54/80)");
+        return fail(NICE_ERR_INVALID, "n outside the base's valid range (or base without a niceonly fast path)");
     switch (base) {
 #define X(b) case b: return (int)nice::unique_fast<b>(lo, hi);
         NICE_FAST_BASES(X)
@@ -1213,7 +1208,7 @@ int nice_check_msd_skippable_inrange(uint32_t base, uint64_t slo, uint64_t shi, 
     u128 rs, re;
     const u128 s = mk(slo, shi), e = mk(elo, ehi);
     if (!nice_fast_base(base) || nice::base_range_cached(base, rs, re) != 1 || s < rs || e > re || s >= e)
-        return fail(NICE_ERR_INVALID, "range outside the base's valid range (or base not 40/50/80)");
+        return fail(NICE_ERR_INVALID, "range outside the base's valid range (or base without a niceonly fast path)");
     if (e - s == 1) return 0;  // a single number is never skipped (msd_prefix_filter.rs:395)
     const u128 l = e - 1;
     const uint64_t llo = lo64(l), lhi = hi64(l);

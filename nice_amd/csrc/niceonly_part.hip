@@ -1,0 +1,63 @@
+// niceonly_part.hip -- the niceonly kernels of the fast bases, one object per
+// part (built with -DNICEONLY_PART=k, k < NICEONLY_NPARTS): part k
+// instantiates niceonly_kernel, msd_level_kernel, msd_fused_kernel,
+// msd_wave_kernel and unique_fast_kernel for the bases of
+// NICE_NICEONLY_PARTk (niceonly_bases.h), so they compile in parallel.
+#include "niceonly_bases.h"
+#include "niceonly_kernels.hpp"
+
+#ifndef NICEONLY_PART
+#error "build with -DNICEONLY_PART=k"
+#endif
+
+#define NICEONLY_CAT2(a, b) a##b
+#define NICEONLY_CAT(a, b) NICEONLY_CAT2(a, b)
+#define NICEONLY_PART_BASES NICEONLY_CAT(NICE_NICEONLY_PART, NICEONLY_PART)
+
+namespace nice {
+
+// The const-modulus instantiations (leaf_desc's constant divisions, the lane
+// walk) take in-range fields on the k = 2 stride table; a wide base's also
+// need the field's end inside the walk's packed high part.
+template <int B>
+static bool const_mod_field(const MsdLaunch &p) {
+    if (const_modulus<B>() == 0 || !p.in_range || p.M != const_modulus<B>()) return false;
+    return wide_n<B>() ? (p.end_hi >> kWideHiBits) == 0 : true;
+}
+
+template <int B>
+hipError_t BaseLaunch<B>::nice(const NiceonlyLaunch &p, int num_cus, hipStream_t s) {
+    return launch_nice(p, ConstBase<B>{}, num_cus, s);
+}
+
+template <int B>
+hipError_t BaseLaunch<B>::msd(const MsdLaunch &p, int num_cus, hipStream_t s, ChunkNode *scratch, u32 cap,
+                              u32 grid) {
+    if (scratch) {  // one workgroup per chunk, all levels in-kernel
+        if (const_mod_field<B>(p))
+            return launch_fused<ConstBase<B>, const_modulus<B>()>(p, ConstBase<B>{}, scratch, cap, grid, s);
+        return launch_fused(p, ConstBase<B>{}, scratch, cap, grid, s);
+    }
+    if (const_mod_field<B>(p)) return launch_msd<ConstBase<B>, const_modulus<B>()>(p, ConstBase<B>{}, num_cus, s);
+    return launch_msd(p, ConstBase<B>{}, num_cus, s);
+}
+
+template <int B>
+hipError_t BaseLaunch<B>::wave(const MsdLaunch &p, const NiceonlyLaunch &c, u32 level0, StackNode *scratch,
+                               u32 grid, int num_cus, hipStream_t s) {
+    if (const_mod_field<B>(p))
+        return launch_wave<ConstBase<B>, const_modulus<B>()>(p, c, level0, scratch, grid, ConstBase<B>{}, num_cus, s);
+    return launch_wave(p, c, level0, scratch, grid, ConstBase<B>{}, num_cus, s);
+}
+
+template <int B>
+hipError_t BaseLaunch<B>::unique(const u64 *n_pairs, u32 count, u32 *out, hipStream_t s) {
+    hipLaunchKernelGGL(unique_fast_kernel<B>, dim3((count + 255) / 256), dim3(256), 0, s, n_pairs, count, out);
+    return hipGetLastError();
+}
+
+#define X(b) template struct BaseLaunch<b>;
+NICEONLY_PART_BASES(X)
+#undef X
+
+}  // namespace nice

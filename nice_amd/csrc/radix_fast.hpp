@@ -1,4 +1,5 @@
-// radix_fast.hpp -- in-range fast paths for the niceonly kernels (b40/50/52/53/54/80).
+// radix_fast.hpp -- in-range fast paths for the niceonly kernels (the fast
+// bases of niceonly_bases.h).
 //
 // Inside a base's valid range n^2 and n^3 have exactly D2 and D3 base-b digits
 // (base_range.rs:14-32), so both fit fixed radix-B = b^2 limb arrays sized at
