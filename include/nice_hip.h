@@ -113,7 +113,30 @@ int nice_process_range_detailed(nice_ctx *ctx, uint64_t start_lo, uint64_t start
  *              run, and survival skew along the field is spread over ranks (the
  *              reference deals descriptors from a shared channel,
  *              client_process_gpu.rs:589-709).
+ *   filter     NICE_FILTER_REFERENCE (0): the reference's MSD filter bit for
+ *              bit, Filter C included -- the MSD x LSD collision check
+ *              (msd_prefix_filter.rs:474-559) that drops a whole range when
+ *              first / b^2 == last / b^2, judging every number of it by the two
+ *              lowest digits of *first*'s square and cube.  That condition
+ *              fixes the high digits of n, not n mod b^2, so the reference can
+ *              drop numbers it has not ruled out.
+ *              NICE_FILTER_SOUND (1): a complete answer.  The recursion ends
+ *              after the square / cube / overlap checks (no Filter C, on the
+ *              device, the host MSD producer and every base), and on the
+ *              compile-time kernels (device MSD, nice_niceonly_fast_base, field
+ *              inside the base's range, stride_k 2) each stride candidate is
+ *              tested against its own low digits instead: rejected iff the
+ *              common leading digits of n^2 and of n^3 over its MSD range plus
+ *              the two lowest digits of its n^2 and n^3 hold a repeat (a range
+ *              of one number rejects nothing).  ranges / range_numbers /
+ *              candidates count as before (every stride candidate of the
+ *              surviving ranges); square_ok counts candidates that passed the
+ *              prefix test with a repeat-free square;
+ *              nice_niceonly_prefix_rejected gives the number rejected.
+ *              Any other value: NICE_ERR_INVALID at submit.
  * Both MSD placements produce the same candidate set. */
+#define NICE_FILTER_REFERENCE 0
+#define NICE_FILTER_SOUND 1
 #define NICE_MSD_FLOOR_ADAPTIVE UINT64_MAX
 #define NICE_MSD_AUTO 0
 #define NICE_MSD_HOST 1
@@ -126,7 +149,7 @@ typedef struct {
     int32_t msd_where;
     uint32_t deal_stride;
     uint32_t deal_offset;
-    uint32_t reserved;
+    uint32_t filter;
 } nice_niceonly_opts;
 
 typedef struct {
@@ -165,6 +188,15 @@ int nice_process_range_niceonly_ex(nice_ctx *ctx, uint64_t start_lo, uint64_t st
                                    uint64_t end_lo, uint64_t end_hi, uint32_t base,
                                    const nice_niceonly_opts *opts, nice_number *out,
                                    size_t cap, size_t *n_out, nice_niceonly_stats *stats);
+/* NICE_FILTER_SOUND: the candidates the per-candidate prefix test rejected in
+ * the niceonly field the calling thread collected last (nice_niceonly_collect
+ * or a synchronous call; thread-local like nice_last_error, so fields collected
+ * on other threads do not disturb it), summed over the context's devices; a
+ * field re-run after a list overflow counts its last run, like the other
+ * statistics.  0 for the reference filter and wherever sound mode runs without
+ * the prefix test (run-time-base kernels, fields outside the base's range,
+ * host MSD, stride_k != 2). */
+uint64_t nice_niceonly_prefix_rejected(void);
 
 /* The coordination server's submit checks for a detailed result
  * (api/src/main.rs:309-359), which nice_process_range_detailed also applies to
@@ -200,6 +232,13 @@ int nice_cpu_process_range_detailed(uint64_t start_lo, uint64_t start_hi, uint64
 int nice_cpu_process_range_niceonly(uint64_t start_lo, uint64_t start_hi, uint64_t end_lo,
                                     uint64_t end_hi, uint32_t base, uint32_t stride_k,
                                     int32_t threads, nice_number *out, size_t cap, size_t *n_out);
+/* The same with nice_niceonly_opts.filter's values: NICE_FILTER_SOUND runs
+ * get_valid_ranges without Filter C and tests every stride candidate of the
+ * larger set (nice_cpu_process_range_niceonly is filter 0). */
+int nice_cpu_process_range_niceonly_ex(uint64_t start_lo, uint64_t start_hi, uint64_t end_lo,
+                                       uint64_t end_hi, uint32_t base, uint32_t stride_k,
+                                       int32_t threads, uint32_t filter, nice_number *out, size_t cap,
+                                       size_t *n_out);
 
 /* Asynchronous fields.  *_submit enqueues a field on the context's devices
  * and returns at once with a ticket; *_collect waits for that field and
@@ -282,6 +321,11 @@ int nice_niceonly_fast_base(uint32_t base);
 int nice_msd_valid_ranges(uint64_t start_lo, uint64_t start_hi, uint64_t end_lo,
                           uint64_t end_hi, uint32_t base, uint64_t floor_size, uint64_t *out,
                           size_t cap, size_t *n_out);
+/* The same with nice_niceonly_opts.filter's values (NICE_FILTER_SOUND: no
+ * Filter C); nice_msd_valid_ranges is filter 0. */
+int nice_msd_valid_ranges_ex(uint64_t start_lo, uint64_t start_hi, uint64_t end_lo,
+                             uint64_t end_hi, uint32_t base, uint64_t floor_size, uint32_t filter,
+                             uint64_t *out, size_t cap, size_t *n_out);
 /* has_duplicate_msd_prefix (msd_prefix_filter.rs:382-563): 1 skippable, 0 not. */
 int nice_msd_skippable(uint64_t start_lo, uint64_t start_hi, uint64_t end_lo, uint64_t end_hi,
                        uint32_t base);
@@ -301,6 +345,13 @@ int nice_check_is_nice_inrange(uint32_t base, uint64_t n_lo, uint64_t n_hi);
 int nice_check_unique_inrange(uint32_t base, uint64_t n_lo, uint64_t n_hi);
 int nice_check_msd_skippable_inrange(uint32_t base, uint64_t start_lo, uint64_t start_hi,
                                      uint64_t end_lo, uint64_t end_hi);
+/* NICE_FILTER_SOUND's per-candidate prefix test by the device code's leaf-mask
+ * and rejection logic (radix_fast.hpp msd_prefix_masks / prefix_rejects, the
+ * stride table's low-digit mask): 1 if n of the MSD leaf [start, end) is
+ * rejected, 0 if not; NICE_ERR_INVALID unless start <= n < end lie inside the
+ * valid range of a nice_niceonly_fast_base base. */
+int nice_check_prefix_reject_inrange(uint32_t base, uint64_t start_lo, uint64_t start_hi,
+                                     uint64_t end_lo, uint64_t end_hi, uint64_t n_lo, uint64_t n_hi);
 /* Limb-count cuts of the production FD kernel (fd2_detailed.hip): the n at
  * which a segment ending there needs a wider (D1, E1, E2) limb layout.  Writes
  * (lo, hi) pairs, returns the count via *n_out.  Bases without an FD kernel: 0. */

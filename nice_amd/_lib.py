@@ -23,6 +23,11 @@ NICE_ERR_NO_DEVICE = 4
 NICE_ERR_MSD_OVERFLOW = 5
 NICE_ERR_BUSY = 6  # *_submit: every slot of the context is in flight
 NICE_MSD_FLOOR_ADAPTIVE = (1 << 64) - 1  # msd_floor: the reference GPU path's AdaptiveFloor
+# nice_niceonly_opts.filter: the reference's MSD filter bit for bit (Filter C
+# included, which can drop numbers it has not ruled out), or the sound filter
+# (no Filter C; a per-candidate prefix test instead, see include/nice_hip.h)
+NICE_FILTER_REFERENCE = 0
+NICE_FILTER_SOUND = 1
 
 # Every symbol include/nice_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -38,6 +43,8 @@ EXPORTS = (
     "nice_cpu_process_range_detailed", "nice_cpu_process_range_niceonly",
     "nice_adaptive_floor_step", "nice_adaptive_floor", "nice_ctx_set_kernel_timing",
     "nice_host_threads", "nice_debug_cgroup_cpus", "nice_debug_force_sib_stride",
+    "nice_niceonly_prefix_rejected", "nice_msd_valid_ranges_ex", "nice_cpu_process_range_niceonly_ex",
+    "nice_check_prefix_reject_inrange",
 )
 
 
@@ -60,7 +67,7 @@ class nice_niceonly_opts(ctypes.Structure):
     _fields_ = [("msd_floor", ctypes.c_uint64), ("chunk_size", ctypes.c_uint64),
                 ("threads", ctypes.c_int32), ("stride_k", ctypes.c_uint32),
                 ("msd_where", ctypes.c_int32), ("deal_stride", ctypes.c_uint32),
-                ("deal_offset", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+                ("deal_offset", ctypes.c_uint32), ("filter", ctypes.c_uint32)]
 
 
 class nice_niceonly_stats(ctypes.Structure):
@@ -124,6 +131,7 @@ def lib():
         "nice_fd_kernel_base": ([u32], i32),
         "nice_niceonly_fast_base": ([u32], i32),
         "nice_msd_valid_ranges": ([u64, u64, u64, u64, u32, u64, P64, sz, PSZ], i32),
+        "nice_msd_valid_ranges_ex": ([u64, u64, u64, u64, u32, u64, u32, P64, sz, PSZ], i32),
         "nice_msd_skippable": ([u64, u64, u64, u64, u32], i32),
         "nice_stride_table": ([u32, u32, P64, P32, sz, PSZ], i32),
         "nice_debug_unique_counts": ([vp, P64, u32, u32, P32], i32),
@@ -132,6 +140,7 @@ def lib():
         "nice_check_is_nice_inrange": ([u32, u64, u64], i32),
         "nice_check_unique_inrange": ([u32, u64, u64], i32),
         "nice_check_msd_skippable_inrange": ([u32, u64, u64, u64, u64], i32),
+        "nice_check_prefix_reject_inrange": ([u32, u64, u64, u64, u64, u64, u64], i32),
         "nice_fd_segment_cuts": ([u32, P64, sz, PSZ], i32),
         "nice_validate_detailed": ([u32, u64, u64, P64, PN, sz], i32),
         "nice_detailed_submit": ([vp, u64, u64, u64, u64, u32, ctypes.POINTER(i32)], i32),
@@ -141,6 +150,8 @@ def lib():
         "nice_niceonly_collect": ([vp, i32, PN, sz, PSZ, ctypes.POINTER(nice_niceonly_stats)], i32),
         "nice_cpu_process_range_detailed": ([u64, u64, u64, u64, u32, i32, P64, PN, sz, PSZ], i32),
         "nice_cpu_process_range_niceonly": ([u64, u64, u64, u64, u32, u32, i32, PN, sz, PSZ], i32),
+        "nice_cpu_process_range_niceonly_ex": ([u64, u64, u64, u64, u32, u32, i32, u32, PN, sz, PSZ], i32),
+        "nice_niceonly_prefix_rejected": ([], u64),
         "nice_adaptive_floor_step": ([ctypes.c_double, ctypes.c_double, ctypes.c_double], ctypes.c_double),
         "nice_adaptive_floor": ([ctypes.POINTER(ctypes.c_double), P32], i32),
         "nice_host_threads": ([], u32),

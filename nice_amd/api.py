@@ -86,15 +86,18 @@ class StrideTable:
         return cls(base, k, m.value, list(buf[: n.value]))
 
 
-def get_valid_ranges(range_: FieldSize, base: int, floor_size: int = 250) -> List[FieldSize]:
-    """get_valid_ranges_recursive (common/src/msd_prefix_filter.rs:583-674)."""
+def get_valid_ranges(range_: FieldSize, base: int, floor_size: int = 250,
+                     filter: str = "reference") -> List[FieldSize]:
+    """get_valid_ranges_recursive (common/src/msd_prefix_filter.rs:583-674);
+    filter="sound": without Filter C (nice_msd_valid_ranges_ex)."""
     s, e = range_.range_start, range_.range_end
+    f = _FILTERS[filter]
     n = ctypes.c_size_t()
-    rc = lib().nice_msd_valid_ranges(*_split(s), *_split(e), base, floor_size, None, 0, n)
+    rc = lib().nice_msd_valid_ranges_ex(*_split(s), *_split(e), base, floor_size, f, None, 0, n)
     if rc not in (_lib.NICE_OK, _lib.NICE_ERR_CAPACITY):
         check(rc)
     buf = (ctypes.c_uint64 * (4 * max(n.value, 1)))()
-    check(lib().nice_msd_valid_ranges(*_split(s), *_split(e), base, floor_size, buf, n.value, n))
+    check(lib().nice_msd_valid_ranges_ex(*_split(s), *_split(e), base, floor_size, f, buf, n.value, n))
     return [FieldSize(buf[4 * i] | (buf[4 * i + 1] << 64), buf[4 * i + 2] | (buf[4 * i + 3] << 64))
             for i in range(n.value)]
 
@@ -125,12 +128,20 @@ class NiceonlyStats:
     msd_threads: int = 0
     # times the field re-ran with grown device lists
     reruns: int = 0
+    # filter="sound": candidates the per-candidate prefix test rejected before
+    # the square test (0 for the reference filter and where sound mode runs
+    # without the test: run-time-base kernels, out-of-range fields, host MSD)
+    prefix_rejected: int = 0
+
+
+_FILTERS = {"reference": _lib.NICE_FILTER_REFERENCE, "sound": _lib.NICE_FILTER_SOUND}
 
 
 def _stats(st) -> NiceonlyStats:
+    """The stats of the niceonly field this thread collected last."""
     return NiceonlyStats(st.ranges, st.range_numbers, st.candidates, st.launches,
                          st.msd_seconds, st.total_seconds, st.square_ok, st.msd_floor,
-                         st.msd_threads, st.reruns)
+                         st.msd_threads, st.reruns, int(lib().nice_niceonly_prefix_rejected()))
 
 
 def host_threads() -> int:
@@ -264,12 +275,17 @@ class GpuContext:
     def niceonly_raw(self, start: int, end: int, base: int, msd_floor: int = 0,
                      chunk_size: int = 0, threads: int = 0, stride_k: int = 0,
                      msd_where: str = "auto", cap: int = 0, deal_stride: int = 0,
-                     deal_offset: int = 0):
+                     deal_offset: int = 0, filter: str = "reference"):
         """Nice numbers of [start, end) ascending, and NiceonlyStats.  With
         deal_stride N > 1 only the field's chunks c with c % N == deal_offset
-        are processed (rank deal_offset of an N-way job, nice_amd/dist.py)."""
+        are processed (rank deal_offset of an N-way job, nice_amd/dist.py).
+        filter="reference" is the reference's MSD filter bit for bit, Filter C
+        included, which can drop numbers it has not ruled out; filter="sound"
+        leaves Filter C out and tests each candidate against its own low
+        digits instead (NICE_FILTER_SOUND, include/nice_hip.h): a complete
+        answer, with NiceonlyStats.prefix_rejected."""
         opts = self._nice_opts(msd_floor, chunk_size, threads, stride_k, msd_where, deal_stride,
-                               deal_offset)
+                               deal_offset, filter)
         st = _lib.nice_niceonly_stats()
         cap = max(cap, self._out_cap, 1024)
         while True:
@@ -286,12 +302,14 @@ class GpuContext:
 
     @staticmethod
     def _nice_opts(msd_floor=0, chunk_size=0, threads=0, stride_k=0, msd_where="auto",
-                   deal_stride=0, deal_offset=0):
+                   deal_stride=0, deal_offset=0, filter="reference"):
         where = {"auto": 0, "host": 1, "device": 2}[msd_where]
+        if filter not in _FILTERS:
+            raise ValueError(f"filter must be one of {sorted(_FILTERS)}")
         if msd_floor == "adaptive":  # client_process_gpu.rs:96-184
             msd_floor = _lib.NICE_MSD_FLOOR_ADAPTIVE
         return _lib.nice_niceonly_opts(msd_floor, chunk_size, threads, stride_k, where,
-                                       deal_stride, deal_offset, 0)
+                                       deal_stride, deal_offset, _FILTERS[filter])
 
     def niceonly_submit(self, start: int, end: int, base: int, **opts) -> int:
         """Enqueue a niceonly field (options as niceonly_raw) and return a
@@ -507,16 +525,17 @@ def process_range_detailed_cpu(range_: FieldSize, base: int, threads: int = 1) -
 
 def process_range_niceonly_cpu(range_: FieldSize, base: int,
                                stride_table: Optional[StrideTable] = None,
-                               threads: int = 1) -> FieldResults:
+                               threads: int = 1, filter: str = "reference") -> FieldResults:
     """process_range_niceonly (client_process.rs:439-465) on the host cores
-    (nice_cpu_process_range_niceonly): MSD floor 250 over the whole range,
-    stride table k from `stride_table` (default 2)."""
+    (nice_cpu_process_range_niceonly_ex): MSD floor 250 over the whole range,
+    stride table k from `stride_table` (default 2); filter="sound" runs the
+    MSD recursion without Filter C."""
     k = stride_table.k if stride_table is not None else 2
     cap = 256
     while True:
         out, n = _cpu_out(cap), ctypes.c_size_t()
-        rc = lib().nice_cpu_process_range_niceonly(*_split(range_.range_start), *_split(range_.range_end),
-                                                    base, k, threads, out, cap, n)
+        rc = lib().nice_cpu_process_range_niceonly_ex(*_split(range_.range_start), *_split(range_.range_end),
+                                                       base, k, threads, _FILTERS[filter], out, cap, n)
         if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
             cap = n.value
             continue

@@ -69,6 +69,9 @@ def parse_args(argv=None):
                    help="niceonly MSD floor: a number (0 = 250, or NICE_GPU_MSD_FLOOR), or "
                         "'adaptive' for the reference GPU path's adaptive floor "
                         "(client_process_gpu.rs:96-184)")
+    p.add_argument("--sound", action="store_true", default=bool(env("NICE_SOUND")),
+                   help="niceonly: the sound filter (no Filter C, which can drop numbers it has not "
+                        "ruled out; a per-candidate prefix test instead) -- a complete answer")
     return p.parse_args(argv)
 
 
@@ -122,7 +125,8 @@ def process_field_sync(claim: DataToClient, mode: SearchMode, args, ctx=None):
         if mode is SearchMode.DETAILED:
             return [api.process_range_detailed_gpu(ctx, field, claim.base)]
         return [api.process_range_niceonly_gpu(ctx, field, claim.base, threads=args.threads,
-                                               msd_floor=args.msd_floor)]
+                                               msd_floor=args.msd_floor,
+                                               filter="sound" if args.sound else "reference")]
     from concurrent.futures import ThreadPoolExecutor
     from .dist import client_chunk_size
     from .types import FieldSize
@@ -137,7 +141,8 @@ def process_field_sync(claim: DataToClient, mode: SearchMode, args, ctx=None):
         table = api.StrideTable.new(claim.base, 2)
 
         def work(c):
-            return api.process_range_niceonly_cpu(c, claim.base, table)
+            return api.process_range_niceonly_cpu(c, claim.base, table,
+                                                  filter="sound" if args.sound else "reference")
     # ctypes releases the GIL inside the library call, so the workers run the
     # chunks in parallel on the host cores
     with ThreadPoolExecutor(max(1, args.threads)) as pool:

@@ -148,12 +148,12 @@ int detailed_cpu(u128 s, u128 e, const BP &bp, int threads, uint64_t *hist, nice
 }
 
 template <class BP>
-int niceonly_cpu(u128 s, u128 e, const BP &bp, uint32_t k, int threads, nice_number *out,
+int niceonly_cpu(u128 s, u128 e, const BP &bp, uint32_t k, int threads, bool sound, nice_number *out,
                  size_t cap, size_t *n_out) {
     // get_valid_ranges over the whole range (msd_prefix_filter.rs:665-674)
     std::vector<std::pair<u128, u128>> ranges;
     nice::MsdFilterT<BP> f(bp);
-    f.valid_ranges(s, e, 0, 250, [&](u128 a, u128 b) { ranges.emplace_back(a, b); });
+    f.valid_ranges(s, e, 0, 250, [&](u128 a, u128 b) { ranges.emplace_back(a, b); }, sound);
     const nice::StrideTable table(bp.b, k);
     const int nt = nthreads(threads, ranges.size());
     std::vector<std::vector<u128>> found(nt);
@@ -216,10 +216,11 @@ extern "C" int nice_cpu_process_range_detailed(uint64_t start_lo, uint64_t start
     return with_base(base, [&](const auto &bp) { return detailed_cpu(s, e, bp, threads, hist, out, cap, n_out); });
 }
 
-extern "C" int nice_cpu_process_range_niceonly(uint64_t start_lo, uint64_t start_hi, uint64_t end_lo,
-                                               uint64_t end_hi, uint32_t base, uint32_t stride_k,
-                                               int32_t threads, nice_number *out, size_t cap,
-                                               size_t *n_out) {
+extern "C" int nice_cpu_process_range_niceonly_ex(uint64_t start_lo, uint64_t start_hi, uint64_t end_lo,
+                                                  uint64_t end_hi, uint32_t base, uint32_t stride_k,
+                                                  int32_t threads, uint32_t filter, nice_number *out,
+                                                  size_t cap, size_t *n_out) {
+    if (filter > NICE_FILTER_SOUND) return cpu_fail(NICE_ERR_INVALID, "bad filter");
     if (!n_out || (cap && !out)) return cpu_fail(NICE_ERR_INVALID, "null output pointer");
     if (base < 2 || base > 128) return cpu_fail(NICE_ERR_INVALID, "base must be in 2..128");
     const uint32_t k = stride_k ? stride_k : 2;
@@ -230,5 +231,14 @@ extern "C" int nice_cpu_process_range_niceonly(uint64_t start_lo, uint64_t start
     if (e < s) return cpu_fail(NICE_ERR_INVALID, "range end before start");
     *n_out = 0;
     if (s == e) return NICE_OK;
-    return with_base(base, [&](const auto &bp) { return niceonly_cpu(s, e, bp, k, threads, out, cap, n_out); });
+    const bool sound = filter == NICE_FILTER_SOUND;
+    return with_base(base, [&](const auto &bp) { return niceonly_cpu(s, e, bp, k, threads, sound, out, cap, n_out); });
+}
+
+extern "C" int nice_cpu_process_range_niceonly(uint64_t start_lo, uint64_t start_hi, uint64_t end_lo,
+                                               uint64_t end_hi, uint32_t base, uint32_t stride_k,
+                                               int32_t threads, nice_number *out, size_t cap,
+                                               size_t *n_out) {
+    return nice_cpu_process_range_niceonly_ex(start_lo, start_hi, end_lo, end_hi, base, stride_k, threads,
+                                              NICE_FILTER_REFERENCE, out, cap, n_out);
 }

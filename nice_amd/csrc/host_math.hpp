@@ -191,10 +191,32 @@ inline std::vector<uint8_t> lsd_bitmap(uint32_t b, uint32_t k) {
     return bm;
 }
 
+// Sound filter's per-candidate prefix test (radix_fast.hpp): the digit mask of
+// the two lowest digits of n^2 and of n^3 for n mod b^2 = x, in mw 32-bit
+// words; returns non-zero when those four digits hold a repeat themselves.
+inline uint32_t low_digit_mask(uint32_t b, uint32_t x, uint32_t *m, int mw) {
+    const uint64_t bb = (uint64_t)b * b;
+    const uint32_t sq = (uint32_t)((uint64_t)x * x % bb), cu = (uint32_t)((uint64_t)sq * x % bb);
+    const uint32_t d[4] = {sq % b, sq / b, cu % b, cu / b};
+    for (int w = 0; w < mw; w++) m[w] = 0;
+    uint32_t dup = 0;
+    for (uint32_t v : d) {
+        const uint32_t bit = 1u << (v & 31);
+        dup |= m[v >> 5] & bit;
+        m[v >> 5] |= bit;
+    }
+    return dup;
+}
+
 // common/src/stride_filter.rs:40-87 (M = (b-1) * b^k, valid residues mod M).
 struct StrideTable {
     uint64_t modulus = 0;
     std::vector<uint32_t> residues;
+    // k >= 2 (b^2 divides M, so a residue fixes n mod b^2): per residue, in
+    // the order of residues[], (b + 31) / 32 words of low_digit_mask, and
+    // the residue with kLowDup set when its low digits repeat themselves.
+    static constexpr uint32_t kLowDup = 1u << 31;
+    std::vector<uint32_t> lowmask, residues_flagged;
 
     StrideTable() {}
     StrideTable(uint32_t b, uint32_t k) {
@@ -207,6 +229,15 @@ struct StrideTable {
         std::vector<uint8_t> lsd = lsd_bitmap(b, k);
         for (uint64_t r = 0; r < modulus; r++)
             if (rok[r % bm1] && lsd[r % bk]) residues.push_back((uint32_t)r);
+        if (k >= 2 && modulus < kLowDup) {
+            const int mw = (int)(b + 31) / 32;
+            lowmask.resize(residues.size() * mw);
+            residues_flagged.resize(residues.size());
+            for (size_t i = 0; i < residues.size(); i++) {
+                const uint32_t dup = low_digit_mask(b, residues[i] % (b * b), &lowmask[i * mw], mw);
+                residues_flagged[i] = residues[i] | (dup ? kLowDup : 0u);
+            }
+        }
     }
     // Global residue-sequence index of the first valid candidate >= x:
     // idx(x) = (x / M) * R + lower_bound(residues, x mod M).
@@ -334,7 +365,9 @@ struct MsdFilterT {
     }
 
     // has_duplicate_msd_prefix on [s, e) (msd_prefix_filter.rs:382-563).
-    bool skippable(u128 s, u128 e) const {
+    // sound: without Filter C, which judges the whole range by first's low
+    // digits (NICE_FILTER_SOUND).
+    bool skippable(u128 s, u128 e, bool sound = false) const {
         if (e - s == 1) return false;
         const u128 first = s, last = e - 1;
         uint32_t fsq[8], fcu[12], lsq[8], lcu[12];
@@ -354,6 +387,7 @@ struct MsdFilterT {
         const uint8_t *cup = cs.d + (cs.n - cp);
         if (dup(cup, cp)) return true;
         if (overlap(sqp, sp, cup, cp)) return true;
+        if (sound) return false;
         // Filter C (k = MSD_LSD_OVERLAP_K_VALUE = 2): uses *first*'s two LSDs.
         const uint64_t bk = (uint64_t)bp.b * bp.b;
         const bool one_class = (uint64_t)(last >> 64) == 0
@@ -372,19 +406,19 @@ struct MsdFilterT {
     // get_valid_ranges_recursive (msd_prefix_filter.rs:583-658), depth <= 22,
     // subdivision factor 2.  Appends surviving [s, e) pairs.
     template <class F>
-    void valid_ranges(u128 s, u128 e, uint32_t depth, u128 floor_size, F &&emit) const {
+    void valid_ranges(u128 s, u128 e, uint32_t depth, u128 floor_size, F &&emit, bool sound = false) const {
         if (depth >= 22 || e - s <= floor_size) {
             emit(s, e);
             return;
         }
-        if (skippable(s, e)) return;
+        if (skippable(s, e, sound)) return;
         if (e - s < floor_size * 2) {
             emit(s, e);
             return;
         }
         const u128 half = (e - s) / 2;
-        valid_ranges(s, s + half, depth + 1, floor_size, emit);
-        valid_ranges(s + half, e, depth + 1, floor_size, emit);
+        valid_ranges(s, s + half, depth + 1, floor_size, emit, sound);
+        valid_ranges(s + half, e, depth + 1, floor_size, emit, sound);
     }
 };
 
@@ -394,17 +428,17 @@ struct MsdFilterT {
 struct MsdRunner {
     virtual ~MsdRunner() {}
     virtual bool skippable(u128 s, u128 e) const = 0;
-    virtual void ranges(u128 s, u128 e, u128 floor_size,
-                        std::vector<std::pair<u128, u128>> &out) const = 0;
+    virtual void ranges(u128 s, u128 e, u128 floor_size, std::vector<std::pair<u128, u128>> &out,
+                        bool sound = false) const = 0;
 };
 template <class BP>
 struct MsdRunnerT : MsdRunner {
     MsdFilterT<BP> f;
     explicit MsdRunnerT(const BP &bp) : f(bp) {}
     bool skippable(u128 s, u128 e) const override { return f.skippable(s, e); }
-    void ranges(u128 s, u128 e, u128 floor_size,
-                std::vector<std::pair<u128, u128>> &out) const override {
-        f.valid_ranges(s, e, 0, floor_size, [&](u128 a, u128 b) { out.emplace_back(a, b); });
+    void ranges(u128 s, u128 e, u128 floor_size, std::vector<std::pair<u128, u128>> &out,
+                bool sound) const override {
+        f.valid_ranges(s, e, 0, floor_size, [&](u128 a, u128 b) { out.emplace_back(a, b); }, sound);
     }
 };
 inline std::unique_ptr<MsdRunner> make_msd(uint32_t base) {

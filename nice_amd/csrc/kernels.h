@@ -105,7 +105,33 @@ struct NiceonlyLaunch {
     NumOut out;
     NiceFinish fin;
 };
-hipError_t launch_niceonly(const NiceonlyLaunch &p, int num_cus, hipStream_t s);
+// Sound filter (NICE_FILTER_SOUND, radix_fast.hpp): what its kernel variants
+// take beside the launch structs.  A leaf carries the digit mask of its
+// common leading digits of n^2 and n^3 (all ones: they repeat, every candidate
+// goes) and whether it holds >= 2 numbers; leaf_masks[] runs parallel to the
+// leaf list, so the reference filter's 24-byte records stay as they are.
+struct LeafMask {
+    uint32_t w[3];
+    uint32_t multi;
+};
+struct SoundLaunch {
+    const uint32_t *residues;     // StrideTable::residues_flagged (bit 31: the low digits repeat)
+    const uint32_t *lowmask;      // StrideTable::lowmask, (base + 31) / 32 words per residue
+    LeafMask *leaf_masks;         // device MSD: parallel to MsdLaunch::leaves
+    unsigned long long *rejected; // candidates the prefix test rejected (counters[96..97], sticky)
+    uint32_t fast;                // the field runs the base's compile-time sound variants
+                                  // (sound_prefix_field), else the run-time-base ones
+    uint32_t prefix_test;         // 0: the recursion without Filter C only (fields that are not
+                                  // `fast`; the probe build's A/B)
+};
+// snd: the sound variants (null: the reference filter's kernels).  The prefix
+// test runs on the compile-time kernels' in-range fields; elsewhere the
+// variants only leave Filter C out.
+hipError_t launch_niceonly(const NiceonlyLaunch &p, int num_cus, hipStream_t s, const SoundLaunch *snd = nullptr);
+struct MsdLaunch;
+// Whether a device-MSD field (bounds, base, table and in_range set) can run the
+// prefix test: a niceonly fast base, in range, on the k = 2 table.
+bool sound_prefix_field(const MsdLaunch &p);
 
 // Device MSD filter (msd_prefix_filter.rs:583-658 as a level-synchronous BFS):
 // one lane per node; leaves (already in stride-index form) are appended to
@@ -133,7 +159,9 @@ struct MsdLaunch {
                                   // [27] square survivors (written at the field's end),
                                   // [28..29] u64 candidates, [30..31] u64 numbers inside
                                   // the ranges (sticky); [32..95] square-survivor partial
-                                  // counts (workgroup b adds to 32 + b % 64, sticky)
+                                  // counts (workgroup b adds to 32 + b % 64, sticky);
+                                  // [96..97] u64 candidates rejected by the sound filter's
+                                  // prefix test (sticky, copied out to mapped words 32..33)
     uint32_t q_cap;
     Leaf *leaves;
     uint32_t leaf_cap;
@@ -147,7 +175,8 @@ struct MsdLaunch {
     uint32_t probe;               // probe build only (NICE_MSD_PROBE): 1 no skip test, 2 no leaf stride math,
                                   // 4 wave kernel: no candidate test
 };
-constexpr uint32_t kMsdCounterWords = 96;
+constexpr uint32_t kMsdCounterWords = 98;
+constexpr uint32_t kMsdMappedWords = 34;
 // A leaf's candidate count is capped at kLeafPiece: longer runs are stored as
 // several leaves, so niceonly_kernel's per-wave sums of 8 leaves fit 32 bits.
 constexpr uint32_t kLeafPiece = 1u << 28;
@@ -163,7 +192,7 @@ uint32_t msd_fused_cap(uint64_t chunk, uint64_t floor_size);
 // cap ChunkNodes) ONE fused launch, one workgroup per chunk; otherwise the
 // init + level kernels.
 hipError_t launch_msd_device(const MsdLaunch &p, int num_cus, hipStream_t s, ChunkNode *scratch = nullptr,
-                             uint32_t cap = 0, uint32_t grid = 0);
+                             uint32_t cap = 0, uint32_t grid = 0, const SoundLaunch *snd = nullptr);
 
 // Large chunks: init + the level BFS down to `level0` (nodes <= 2^26 numbers,
 // enough roots to fill the chip), then msd_wave_kernel: the recursion below
@@ -173,7 +202,7 @@ hipError_t launch_msd_device(const MsdLaunch &p, int num_cus, hipStream_t s, Chu
 // in `scratch` (msd_wave_scratch_bytes(grid)).  Leaves of the BFS levels go
 // to p.leaves and are tested by the same launch.
 hipError_t launch_msd_wave(const MsdLaunch &p, const NiceonlyLaunch &c, uint32_t level0, void *scratch,
-                           uint32_t grid, int num_cus, hipStream_t s);
+                           uint32_t grid, int num_cus, hipStream_t s, const SoundLaunch *snd = nullptr);
 size_t msd_wave_scratch_bytes(uint32_t grid);
 uint32_t msd_wave_waves_per_group();
 

@@ -108,8 +108,9 @@ struct MsdBuf {
     void *wscratch = nullptr;  // msd_wave_kernel work stacks
     size_t wscratch_bytes = 0;
     nice::Leaf *leaves = nullptr;
-    uint32_t *counters = nullptr;  // 32 words
-    uint32_t q_cap = 0, leaf_cap = 0;
+    nice::LeafMask *leaf_masks = nullptr;  // sound filter: parallel to leaves (allocated on first use)
+    uint32_t *counters = nullptr;  // kMsdCounterWords
+    uint32_t q_cap = 0, leaf_cap = 0, mask_cap = 0;
     uint64_t scratch_nodes = 0;
     // counters / nice count not known to be zero (first use, or a field that
     // did not end in the candidate kernel's epilogue)
@@ -168,6 +169,8 @@ struct Device {
     Slot slot[kSlots];
     std::map<uint32_t, uint32_t *> residues;  // base*8+k -> device residue table
     std::map<uint32_t, uint32_t *> ranks;     // base*8+k -> lower_bound(residues, r), r in [0, M]
+    // sound filter: base*8+k -> StrideTable::residues_flagged followed by ::lowmask
+    std::map<uint32_t, uint32_t *> lowtabs;
     LeafBuf desc[2];
     int desc_next = 0;
     nice_kernel_stats last{};
@@ -222,6 +225,7 @@ struct NiceJob {
     std::vector<Entry> all;
     bool adapt = false;            // host-MSD field on the adaptive floor: update it at collect
     uint32_t reruns = 0;           // times the field was re-run with grown device lists
+    uint64_t rejected = 0;         // sound filter: candidates the prefix test rejected
 };
 
 }  // namespace
@@ -330,8 +334,15 @@ int ensure_desc(LeafBuf &b, uint32_t cap) {
     return NICE_OK;
 }
 
-int ensure_msd(Slot &sl, uint32_t q_cap, uint32_t leaf_cap, uint64_t scratch_nodes, size_t wscratch_bytes = 0) {
+int ensure_msd(Slot &sl, uint32_t q_cap, uint32_t leaf_cap, uint64_t scratch_nodes, size_t wscratch_bytes = 0,
+               bool masks = false) {
     MsdBuf &m = sl.msd;
+    if (masks && m.mask_cap < std::max(leaf_cap, m.leaf_cap)) {
+        HIPCHK(hipStreamSynchronize(sl.nstream));
+        if (m.leaf_masks) HIPCHK(hipFree(m.leaf_masks));
+        m.mask_cap = std::max(leaf_cap, m.leaf_cap);
+        HIPCHK(hipMalloc(&m.leaf_masks, (size_t)m.mask_cap * sizeof(nice::LeafMask)));
+    }
     if (!m.counters) HIPCHK(hipMalloc(&m.counters, nice::kMsdCounterWords * 4));
     if (m.wscratch_bytes < wscratch_bytes) {
         HIPCHK(hipStreamSynchronize(sl.nstream));
@@ -386,7 +397,8 @@ int slot_init(Device &d, Slot &sl, const Slot *share) {
     HIPCHK(hipHostMalloc(&sl.h_fin, kFinWords * 8, hipHostMallocMapped | hipHostMallocCoherent));
     memset(sl.h_fin, 0, kFinWords * 8);
     HIPCHK(hipHostGetDevicePointer((void **)&sl.d_fin, sl.h_fin, 0));
-    HIPCHK(hipHostMalloc(&sl.h_msd, 32 * 4, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(hipHostMalloc(&sl.h_msd, nice::kMsdMappedWords * 4, hipHostMallocMapped | hipHostMallocCoherent));
+    memset(sl.h_msd, 0, nice::kMsdMappedWords * 4);
     HIPCHK(hipHostGetDevicePointer((void **)&sl.d_msd_mapped, sl.h_msd, 0));
     HIPCHK(hipHostMalloc(&sl.h_nice, 4, hipHostMallocMapped | hipHostMallocCoherent));
     HIPCHK(hipHostGetDevicePointer((void **)&sl.d_nice_mapped, sl.h_nice, 0));
@@ -426,6 +438,7 @@ void device_free(Device &d) {
     }
     for (auto &kv : d.residues) (void)hipFree(kv.second);
     for (auto &kv : d.ranks) (void)hipFree(kv.second);
+    for (auto &kv : d.lowtabs) (void)hipFree(kv.second);
     for (auto &b : d.desc) {
         if (b.h) {
             (void)hipHostFree(b.h);
@@ -437,6 +450,7 @@ void device_free(Device &d) {
         for (auto &q : sl.msd.q)
             if (q) (void)hipFree(q);
         if (sl.msd.leaves) (void)hipFree(sl.msd.leaves);
+        if (sl.msd.leaf_masks) (void)hipFree(sl.msd.leaf_masks);
         if (sl.msd.counters) (void)hipFree(sl.msd.counters);
         if (sl.msd.scratch) (void)hipFree(sl.msd.scratch);
         if (sl.stream && sl.own_stream) (void)hipStreamDestroy(sl.stream);
@@ -1097,6 +1111,17 @@ int detailed_collect_locked(nice_ctx *ctx, int ticket, uint64_t *hist, nice_numb
 
 }  // namespace
 
+template <int B>
+static int prefix_reject_host(u128 s, u128 l, u128 n) {
+    constexpr int MW = nice::Radix<B>::MW;
+    uint32_t pm[MW] = {}, low[MW];
+    const uint32_t multi = l > s ? 1u : 0u;
+    if (multi && nice::msd_prefix_masks<B>(lo64(s), hi64(s), lo64(l), hi64(l), pm))
+        for (int w = 0; w < MW; w++) pm[w] = ~0u;  // the prefix repeats: every candidate goes
+    const uint32_t dup = nice::low_digit_mask(B, (uint32_t)(n % ((uint32_t)B * B)), low, MW);
+    return nice::prefix_rejects<MW>(pm, multi, low, dup) ? 1 : 0;
+}
+
 extern "C" {
 
 int nice_validate_detailed(uint32_t base, uint64_t size_lo, uint64_t size_hi, const uint64_t *hist,
@@ -1220,6 +1245,20 @@ int nice_check_msd_skippable_inrange(uint32_t base, uint64_t slo, uint64_t shi, 
     }
 }
 
+int nice_check_prefix_reject_inrange(uint32_t base, uint64_t slo, uint64_t shi, uint64_t elo, uint64_t ehi,
+                                     uint64_t nlo, uint64_t nhi) {
+    u128 rs, re;
+    const u128 s = mk(slo, shi), e = mk(elo, ehi), n = mk(nlo, nhi);
+    if (!nice_fast_base(base) || nice::base_range_cached(base, rs, re) != 1 || s < rs || e > re || n < s || n >= e)
+        return fail(NICE_ERR_INVALID, "leaf or n outside the base's valid range (or base without a niceonly fast path)");
+    switch (base) {
+#define X(b) case b: return prefix_reject_host<b>(s, e - 1, n);
+        NICE_FAST_BASES(X)
+#undef X
+    default: return NICE_ERR_INVALID;
+    }
+}
+
 int nice_fd_segment_cuts(uint32_t base, uint64_t *out, size_t cap, size_t *n_out) {
     std::vector<u128> c(8);
     const size_t n = nice::fd2_cuts(base, c.data(), c.size());
@@ -1238,9 +1277,15 @@ int nice_msd_skippable(uint64_t slo, uint64_t shi, uint64_t elo, uint64_t ehi, u
 
 int nice_msd_valid_ranges(uint64_t slo, uint64_t shi, uint64_t elo, uint64_t ehi, uint32_t base,
                           uint64_t floor_size, uint64_t *out, size_t cap, size_t *n_out) {
-    if (base < 2 || base > 128 || mk(slo, shi) >= mk(elo, ehi)) return fail(NICE_ERR_INVALID, "bad args");
+    return nice_msd_valid_ranges_ex(slo, shi, elo, ehi, base, floor_size, NICE_FILTER_REFERENCE, out, cap, n_out);
+}
+
+int nice_msd_valid_ranges_ex(uint64_t slo, uint64_t shi, uint64_t elo, uint64_t ehi, uint32_t base,
+                             uint64_t floor_size, uint32_t filter, uint64_t *out, size_t cap, size_t *n_out) {
+    if (base < 2 || base > 128 || mk(slo, shi) >= mk(elo, ehi) || filter > NICE_FILTER_SOUND)
+        return fail(NICE_ERR_INVALID, "bad args");
     std::vector<std::pair<u128, u128>> rs;
-    nice::make_msd(base)->ranges(mk(slo, shi), mk(elo, ehi), floor_size, rs);
+    nice::make_msd(base)->ranges(mk(slo, shi), mk(elo, ehi), floor_size, rs, filter == NICE_FILTER_SOUND);
     size_t n = rs.size();
     for (size_t i = 0; i < n && i < cap; i++) {
         out[4 * i] = lo64(rs[i].first);
@@ -1450,6 +1495,7 @@ int niceonly_enqueue(nice_ctx *ctx, int t, NiceJob &job) {
     const uint64_t deal_stride = opts && opts->deal_stride ? opts->deal_stride : 1;
     const uint64_t deal_offset = opts ? opts->deal_offset : 0;
     if (deal_offset >= deal_stride) return fail(NICE_ERR_INVALID, "deal_offset must be < deal_stride");
+    const bool sound = opts && opts->filter == NICE_FILTER_SOUND;
     // This caller's chunks of the field's grid: c = deal_offset + i * deal_stride.
     const u128 nchunks_field = (e - s + chunk - 1) / chunk;
     const u128 mine128 = deal_offset < nchunks_field
@@ -1465,6 +1511,7 @@ int niceonly_enqueue(nice_ctx *ctx, int t, NiceJob &job) {
     job.all.clear();
     job.empty = false;
     job.collected = false;
+    job.rejected = 0;
     job.st = st;
     auto finish_submit = [&]() { return NICE_OK; };
     if (nice::residue_filter(base).empty() || mine == 0) {  // client_process_gpu.rs:525-531
@@ -1497,6 +1544,13 @@ int niceonly_enqueue(nice_ctx *ctx, int t, NiceJob &job) {
             HIPCHK(hipMalloc(&p, rank.size() * 4));
             HIPCHK(hipMemcpy(p, rank.data(), rank.size() * 4, hipMemcpyHostToDevice));
             d.ranks[base * 8 + k] = p;
+        }
+        if (sound && !table->lowmask.empty() && !d.lowtabs.count(base * 8 + k)) {
+            uint32_t *p;
+            HIPCHK(hipMalloc(&p, ((size_t)R + table->lowmask.size()) * 4));
+            HIPCHK(hipMemcpy(p, table->residues_flagged.data(), (size_t)R * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(p + R, table->lowmask.data(), table->lowmask.size() * 4, hipMemcpyHostToDevice));
+            d.lowtabs[base * 8 + k] = p;
         }
     }
 
@@ -1565,14 +1619,26 @@ int niceonly_enqueue(nice_ctx *ctx, int t, NiceJob &job) {
             wleaf_cap = per * (1 + (fl >> 28)) + 64;
         }
         const uint64_t nbatches = nbatches_of(mine, cpb);
+        // Sound filter: the prefix test where the field allows it (the probe
+        // build's NICE_SOUND_NOPREFIX leaves it off, for the A/B)
+        bool sound_fast = false;
+        if (sound && !table->lowmask.empty()) {
+            nice::MsdLaunch q{};
+            q.end_hi = hi64(e);
+            q.M = (uint32_t)M;
+            q.base = base;
+            q.in_range = in_range;
+            sound_fast = nice::sound_prefix_field(q);
+        }
+        const bool prefix = sound_fast && !nice::probe_set("NICE_SOUND_NOPREFIX");
         for (size_t i = 0; i < ctx->devs.size(); i++) {
             Device &d = ctx->devs[i];
             HIPCHK(hipSetDevice(d.id));
             const uint64_t fgrid = std::min<uint64_t>(cpb, (uint64_t)d.num_cus * 4);
-            int r = fcap   ? ensure_msd(d.slot[t], 0, (uint32_t)leaf_cap, fgrid * 2 * fcap)
+            int r = fcap   ? ensure_msd(d.slot[t], 0, (uint32_t)leaf_cap, fgrid * 2 * fcap, 0, prefix)
                     : wave ? ensure_msd(d.slot[t], (uint32_t)per, (uint32_t)wleaf_cap, 0,
-                                        nice::msd_wave_scratch_bytes(wgrid))
-                           : ensure_msd(d.slot[t], (uint32_t)per, (uint32_t)leaf_cap, 0);
+                                        nice::msd_wave_scratch_bytes(wgrid), prefix)
+                           : ensure_msd(d.slot[t], (uint32_t)per, (uint32_t)leaf_cap, 0, 0, prefix);
             if (r) return r;
             if (i < nbatches) {
                 job.used[i] = 1;
@@ -1615,6 +1681,18 @@ int niceonly_enqueue(nice_ctx *ctx, int t, NiceJob &job) {
             mp.base = base;
             mp.in_range = in_range;
             mp.probe = (uint32_t)nice::probe_knob("NICE_MSD_PROBE", 0);
+            nice::SoundLaunch sl{};
+            if (sound) {
+                if (prefix) {
+                    sl.residues = d.lowtabs[base * 8 + k];
+                    sl.lowmask = sl.residues + R;
+                    sl.leaf_masks = mb.leaf_masks;
+                }
+                sl.rejected = (unsigned long long *)(mb.counters + 96);
+                sl.fast = sound_fast ? 1u : 0u;
+                sl.prefix_test = prefix ? 1u : 0u;
+            }
+            const nice::SoundLaunch *snd = sound ? &sl : nullptr;
             nice::NiceonlyLaunch p{};
             if (wave) {
                 p.residues = mp.residues;
@@ -1627,15 +1705,15 @@ int niceonly_enqueue(nice_ctx *ctx, int t, NiceJob &job) {
                                                 d.slot[t].d_nice_done}
                              : nice::NiceFinish{nullptr, nullptr, mb.counters, d.slot[t].d_nice_done};
                 hipError_t err = nice::launch_msd_wave(mp, p, wlevel, mb.wscratch, wgrid, d.num_cus,
-                                                       d.slot[t].nstream);
+                                                       d.slot[t].nstream, snd);
                 if (err != hipSuccess)
                     return fail(NICE_ERR_HIP, std::string("msd wave launch: ") + hipGetErrorString(err));
                 st.launches++;
                 continue;
             }
             const uint32_t fgrid = (uint32_t)std::min<uint64_t>(mp.nchunks, (uint64_t)d.num_cus * 4);
-            hipError_t err = fcap ? nice::launch_msd_device(mp, d.num_cus, d.slot[t].nstream, mb.scratch, fcap, fgrid)
-                                  : nice::launch_msd_device(mp, d.num_cus, d.slot[t].nstream);
+            hipError_t err = fcap ? nice::launch_msd_device(mp, d.num_cus, d.slot[t].nstream, mb.scratch, fcap, fgrid, snd)
+                                  : nice::launch_msd_device(mp, d.num_cus, d.slot[t].nstream, nullptr, 0, 0, snd);
             if (err != hipSuccess) return fail(NICE_ERR_HIP, std::string("msd launch: ") + hipGetErrorString(err));
             p.leaves = mb.leaves;
             p.n_leaves_dev = mb.counters + 24;
@@ -1651,7 +1729,7 @@ int niceonly_enqueue(nice_ctx *ctx, int t, NiceJob &job) {
             p.fin = last ? nice::NiceFinish{d.slot[t].d_msd_mapped, d.slot[t].d_nice_mapped, mb.counters,
                                             d.slot[t].d_nice_done}
                          : nice::NiceFinish{nullptr, nullptr, mb.counters, d.slot[t].d_nice_done};
-            err = nice::launch_niceonly(p, d.num_cus, d.slot[t].nstream);
+            err = nice::launch_niceonly(p, d.num_cus, d.slot[t].nstream, snd);
             if (err != hipSuccess) return fail(NICE_ERR_HIP, std::string("niceonly launch: ") + hipGetErrorString(err));
             st.launches++;
         }
@@ -1701,7 +1779,7 @@ int niceonly_enqueue(nice_ctx *ctx, int t, NiceJob &job) {
                     if (i >= mine) break;
                     u128 cs, ce;
                     chunk_range(i, cs, ce);
-                    filt->ranges(cs, ce, floor_size, local);
+                    filt->ranges(cs, ce, floor_size, local, sound);
                     if (local.size() >= 4096) {
                         std::lock_guard<std::mutex> g(qmu);
                         queue.push_back(std::move(local));
@@ -1838,6 +1916,11 @@ int niceonly_gather(nice_ctx *ctx, NiceJob &job, int t, std::vector<uint32_t> &c
             job.st.candidates += cand;
             job.st.range_numbers += nums;
             job.st.square_ok += c[27];
+            if (job.has_opts && job.opts.filter == NICE_FILTER_SOUND) {
+                uint64_t rj;
+                std::memcpy(&rj, c + 32, 8);
+                job.rejected += rj;
+            }
         }
         const uint32_t cnt = *sl.h_nice;
         counts[i] = cnt;
@@ -1865,6 +1948,9 @@ extern "C" {
 
 namespace {
 
+// nice_niceonly_prefix_rejected(): the calling thread's last collected field
+thread_local uint64_t t_prefix_rejected = 0;
+
 int niceonly_submit_args(nice_ctx *ctx, uint64_t start_lo, uint64_t start_hi, uint64_t end_lo, uint64_t end_hi,
                          uint32_t base, const nice_niceonly_opts *opts, bool wait, int *ticket) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -1875,6 +1961,8 @@ int niceonly_submit_args(nice_ctx *ctx, uint64_t start_lo, uint64_t start_hi, ui
         return fail(NICE_ERR_INVALID, "Range has invalid bounds, range_start must be < range_end");
     if (opts && opts->deal_offset >= (opts->deal_stride ? opts->deal_stride : 1u))
         return fail(NICE_ERR_INVALID, "deal_offset must be < deal_stride");
+    if (opts && opts->filter > NICE_FILTER_SOUND)
+        return fail(NICE_ERR_INVALID, "filter must be NICE_FILTER_REFERENCE or NICE_FILTER_SOUND");
     const uint64_t floor_size = resolve_floor(opts);
     std::unique_lock<std::mutex> lock(ctx->mu);
     int t = -1;
@@ -1984,6 +2072,7 @@ int niceonly_collect_locked(nice_ctx *ctx, int t, nice_number *out, size_t cap, 
         }
     }
     if (stats) *stats = job.st;
+    t_prefix_rejected = job.rejected;
     const int rc = emit_list(job.all, out, cap, n_out);
     if (rc == NICE_ERR_CAPACITY) return rc;  // kept: the caller retries with room
     job.active = false;
@@ -1999,6 +2088,8 @@ int nice_niceonly_submit(nice_ctx *ctx, uint64_t start_lo, uint64_t start_hi, ui
                          uint64_t end_hi, uint32_t base, const nice_niceonly_opts *opts, int *ticket) {
     return niceonly_submit_args(ctx, start_lo, start_hi, end_lo, end_hi, base, opts, false, ticket);
 }
+
+uint64_t nice_niceonly_prefix_rejected(void) { return t_prefix_rejected; }
 
 int nice_niceonly_collect(nice_ctx *ctx, int t, nice_number *out, size_t cap, size_t *n_out,
                           nice_niceonly_stats *stats) {

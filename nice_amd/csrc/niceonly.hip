@@ -43,8 +43,34 @@ void launch_msd_init(const MsdLaunch &p, hipStream_t s) {
     hipLaunchKernelGGL(msd_init_kernel, dim3(256), dim3(256), 0, s, p);
 }
 
-hipError_t launch_niceonly(const NiceonlyLaunch &p, int num_cus, hipStream_t s) {
+// A sound field's kernels: the base's compile-time variants where the prefix
+// test can run (SoundLaunch::fast, which the caller sets only for device-MSD
+// fields that sound_prefix_field accepts), else the run-time-base variants,
+// which only leave Filter C out.
+bool sound_prefix_field(const MsdLaunch &p) {
+    switch (p.base) {
+#define X(b) case b: return BaseLaunch<b>::sound_fast(p);
+        NICE_NICEONLY_BASES(X)
+#undef X
+    default: return false;
+    }
+}
+
+hipError_t launch_niceonly(const NiceonlyLaunch &p, int num_cus, hipStream_t s, const SoundLaunch *snd) {
     if (!p.n_leaves_dev && p.n_leaves == 0 && !p.fin.done) return hipSuccess;
+    if (snd) {
+        if (snd->fast && p.n_leaves_dev) {
+            switch (p.base) {
+#define X(b) case b: return BaseLaunch<b>::nice_sound(p, num_cus, s, *snd);
+                NICE_NICEONLY_BASES(X)
+#undef X
+            default: break;
+            }
+        }
+        SoundLaunch off = *snd;
+        off.prefix_test = 0;
+        return launch_nice<GenericBase>(p, make_generic(p.base), num_cus, s, off);
+    }
     switch (p.base) {
 #define X(b) case b: return BaseLaunch<b>::nice(p, num_cus, s);
         NICE_NICEONLY_BASES(X)
@@ -54,9 +80,23 @@ hipError_t launch_niceonly(const NiceonlyLaunch &p, int num_cus, hipStream_t s) 
 }
 
 hipError_t launch_msd_wave(const MsdLaunch &p, const NiceonlyLaunch &c, uint32_t level0, void *scratch,
-                           uint32_t grid, int num_cus, hipStream_t s) {
+                           uint32_t grid, int num_cus, hipStream_t s, const SoundLaunch *snd) {
     if (level0 > 22 || (p.nchunks << level0) >> level0 != p.nchunks) return hipErrorInvalidValue;
     StackNode *st = (StackNode *)scratch;
+    if (snd) {
+        if (snd->fast) {
+            switch (p.base) {
+#define X(b) case b: return BaseLaunch<b>::wave_sound(p, c, level0, st, grid, num_cus, s, *snd);
+                NICE_NICEONLY_BASES(X)
+#undef X
+            default: break;
+            }
+        }
+        SoundLaunch off = *snd;
+        off.prefix_test = 0;
+        return launch_wave<GenericBase, 0>(p, c, level0, st, grid, make_generic(p.base), num_cus, s,
+                                                 off);
+    }
     switch (p.base) {
 #define X(b) case b: return BaseLaunch<b>::wave(p, c, level0, st, grid, num_cus, s);
         NICE_NICEONLY_BASES(X)
@@ -78,8 +118,22 @@ u32 msd_fused_cap(u64 chunk, u64 floor_size) {
 }
 
 hipError_t launch_msd_device(const MsdLaunch &p, int num_cus, hipStream_t s, ChunkNode *scratch,
-                             u32 cap, u32 grid) {
+                             u32 cap, u32 grid, const SoundLaunch *snd) {
     if (scratch && p.nchunks > 0xffffffffull) return hipErrorInvalidValue;
+    if (snd) {
+        if (snd->fast) {
+            switch (p.base) {
+#define X(b) case b: return BaseLaunch<b>::msd_sound(p, num_cus, s, scratch, cap, grid, *snd);
+                NICE_NICEONLY_BASES(X)
+#undef X
+            default: break;
+            }
+        }
+        SoundLaunch off = *snd;
+        off.prefix_test = 0;
+        if (scratch) return launch_fused<GenericBase, 0>(p, make_generic(p.base), scratch, cap, grid, s, off);
+        return launch_msd<GenericBase, 0>(p, make_generic(p.base), num_cus, s, off);
+    }
     switch (p.base) {
 #define X(b) case b: return BaseLaunch<b>::msd(p, num_cus, s, scratch, cap, grid);
         NICE_NICEONLY_BASES(X)

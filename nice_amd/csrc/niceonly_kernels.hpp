@@ -75,6 +75,58 @@ struct WideN<ConstBase<B>> {
 // into one queue word (LeafW).
 constexpr u32 kWideHiBits = 12, kWideG0Bits = 20;
 
+// Sound filter (NICE_FILTER_SOUND; kernels.h SoundLaunch, radix_fast.hpp): the
+// kernels below take a trailing parameter pack, empty for the reference filter
+// -- whose instantiations keep their signature and compile to what they were --
+// and one SoundLaunch for the sound variants.  Those leave Filter C out of the
+// recursion; with the prefix test on (compile-time base, in-range field, k = 2
+// table) a leaf carries its prefix mask and every stride candidate is tested
+// against its residue's low-digit mask before the square test.  What a sound
+// variant keeps per lane is in SoundCtx<true>; SoundCtx<false> is empty and
+// the shared code touches it only under `if constexpr (SOUND)`.
+template <bool SOUND>
+struct SoundCtx {};
+template <>
+struct SoundCtx<true> {
+    const SoundLaunch *snd;
+    bool pt;      // the prefix test is on (uniform over the launch)
+    u32 rej;      // candidates this lane rejected
+    LeafMask lm;  // the mask of the lane's node or leaf
+};
+template <class G>
+__device__ __forceinline__ SoundCtx<false> sound_ctx(u32) { return {}; }
+template <class G>
+__device__ __forceinline__ SoundCtx<true> sound_ctx(u32 in_range, const SoundLaunch &snd) {
+    return SoundCtx<true>{&snd, IsConst<G>::value && in_range && snd.prefix_test, 0u, LeafMask{{0, 0, 0}, 0}};
+}
+
+// A leaf's prefix mask from its queue word(s) against candidate idx's residue
+// words: the candidate is rejected.
+template <int B>
+__device__ __forceinline__ bool cand_rejected(const SoundLaunch &snd, const u32 (&pm)[Radix<B>::MW], u32 multi,
+                                              u32 idx) {
+    constexpr int MW = Radix<B>::MW;
+    u32 low[MW];
+#pragma unroll
+    for (int w = 0; w < MW; w++) low[w] = snd.lowmask[idx * MW + w];
+    return prefix_rejects<MW>(pm, multi, low, snd.residues[idx] >> 31);
+}
+
+// This workgroup's rejected candidates (per-lane counts) into the field's
+// counter: one LDS add per wave, one global add per workgroup.  Every thread
+// calls it (a barrier inside).
+__device__ __forceinline__ void rejected_flush(unsigned long long *ctr, u32 mine) {
+    __shared__ unsigned long long wg_sum;
+    if (threadIdx.x == 0) wg_sum = 0;
+    __syncthreads();
+    u64 v = mine;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&wg_sum, (unsigned long long)v);
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_sum) atomicAdd(ctr, wg_sum);
+}
+
 // ---------------------------------------------------------------------------
 // Candidate check kernel
 // ---------------------------------------------------------------------------
@@ -167,9 +219,11 @@ __device__ __forceinline__ CandWave cand_wave(const NiceonlyLaunch &p, ulonglong
 // count 0), 64 per round: lane k finds its leaf by a uniform binary search over
 // the wave's exclusive prefix (cross-lane reads), rebuilds n = b0 + ((g0 + j) /
 // R) * M + residues[(g0 + j) % R] and tests it (client_process.rs:222-253).
-template <class G, u32 LPW>
+// SOUND with the prefix test on: sc->lm is the lane's leaf mask; a rejected
+// candidate skips the square test and counts in sc->rej.
+template <class G, u32 LPW, bool SOUND = false>
 __device__ __forceinline__ void check_leaf_group(const NiceonlyLaunch &p, const G &g, const Leaf &lf, u32 lane,
-                                                 CandWave &cw) {
+                                                 CandWave &cw, SoundCtx<SOUND> *sc = nullptr) {
     u32 incl = lf.count;
 #pragma unroll
     for (int o = 1; o < (int)LPW; o <<= 1) {
@@ -191,6 +245,15 @@ __device__ __forceinline__ void check_leaf_group(const NiceonlyLaunch &p, const 
         const u32 g0 = __shfl(lf.g0, lo);
         const u64 b0lo = __shfl(lf.b0_lo, lo), b0hi = __shfl(lf.b0_hi, lo);
         u64 n_lo = 0, n_hi = 0;
+        bool gone = false;  // SOUND: rejected by the prefix test
+        [[maybe_unused]] LeafMask mk;
+        if constexpr (SOUND && IsConst<G>::value) {
+            if (sc->pt) {  // lane lo holds the leaf's mask (read with every lane active)
+#pragma unroll
+                for (int w = 0; w < 3; w++) mk.w[w] = __shfl(sc->lm.w[w], lo);
+                mk.multi = __shfl(sc->lm.multi, lo);
+            }
+        }
         if (k < total) {
             const u32 gi = g0 + j;
             const u32 cyc = (u32)(((u64)gi * cw.r_magic) >> cw.r_shift);
@@ -198,12 +261,22 @@ __device__ __forceinline__ void check_leaf_group(const NiceonlyLaunch &p, const 
             n_lo = b0lo;
             n_hi = b0hi;
             add_u128(n_lo, n_hi, (u64)cyc * p.M + p.residues[idx]);
+            if constexpr (SOUND && IsConst<G>::value) {
+                if (sc->pt) {
+                    constexpr int MW = Radix<IsConst<G>::base>::MW;
+                    u32 pm[MW];
+#pragma unroll
+                    for (int w = 0; w < MW; w++) pm[w] = mk.w[w];
+                    gone = cand_rejected<IsConst<G>::base>(*sc->snd, pm, mk.multi, idx);
+                    sc->rej += gone ? 1u : 0u;
+                }
+            }
         }
         if constexpr (IsConst<G>::value) {
             if (p.in_range) {  // wave-uniform
                 // n^2 first; the few survivors queue for a full-wave cube pass
                 bool sq = false;
-                if (k < total) {
+                if (k < total && !gone) {
                     if constexpr (PairTab<G>::on) sq = square_ok_tab<IsConst<G>::base>(n_lo, n_hi, cw.tab);
                     else sq = square_ok<IsConst<G>::base>(n_lo, n_hi);
                 }
@@ -248,6 +321,9 @@ __device__ __forceinline__ void square_ok_flush(u32 *ctr, u32 *wg_sum, u32 waves
 // (count_mapped set): the MSD counters and the nice count out, then re-zeroed
 // for the slot's next field.  Batch end: only the per-batch leaf-record count
 // is re-zeroed, for the next batch.
+// SOUND: the prefix test's rejected count (counters[96..97]) goes out to mapped
+// words 32..33 and is re-zeroed with the rest.
+template <bool SOUND = false>
 __device__ __forceinline__ void nice_launch_finish(const NiceFinish &fin, u32 *count) {
     __shared__ u32 last;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -269,6 +345,12 @@ __device__ __forceinline__ void nice_launch_finish(const NiceFinish &fin, u32 *c
                 fin.msd_mapped[w] = w == 27 ? part : v;
                 if (w >= 24) __hip_atomic_store(&ctr[w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
+            if constexpr (SOUND) {
+                if (w >= 32 && w < 34) {
+                    fin.msd_mapped[w] = __hip_atomic_load(&ctr[64 + w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(&ctr[64 + w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
         }
         if (w == 0) {
             *fin.count_mapped = __hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -280,9 +362,10 @@ __device__ __forceinline__ void nice_launch_finish(const NiceFinish &fin, u32 *c
     done_reset(fin.done);
 }
 
-template <class G>
+template <class G, class... S>
 __global__ void __launch_bounds__(256)
-niceonly_kernel(NiceonlyLaunch p, G g) {
+niceonly_kernel(NiceonlyLaunch p, G g, S... snd) {
+    constexpr bool SOUND = sizeof...(S) != 0;
     const u32 lane = threadIdx.x & 63;
     const u32 gwave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const u32 nwaves = (gridDim.x * blockDim.x) >> 6;
@@ -291,6 +374,7 @@ niceonly_kernel(NiceonlyLaunch p, G g) {
     __shared__ uint2 tab[PairTab<G>::N];
     __shared__ u32 sq_sum;
     if (threadIdx.x == 0) sq_sum = 0;
+    [[maybe_unused]] SoundCtx<SOUND> sc = sound_ctx<G>(p.in_range, snd...);
     pair_tab_fill<G>(tab);  // (ends with a barrier)
     CandWave cw = cand_wave(p, cq[threadIdx.x >> 6], tab);
     // LPW leaves per wave (lanes >= LPW carry count 0): at the CPU path's
@@ -301,11 +385,20 @@ niceonly_kernel(NiceonlyLaunch p, G g) {
         const u32 li = base + lane;
         Leaf lf{0, 0, 0, 0};
         if (lane < LPW && li < n_leaves) lf = p.leaves[li];
-        check_leaf_group<G, LPW>(p, g, lf, lane, cw);
+        if constexpr (SOUND) {
+            sc.lm = LeafMask{{0, 0, 0}, 0};
+            if (sc.pt && lane < LPW && li < n_leaves) sc.lm = sc.snd->leaf_masks[li];
+            check_leaf_group<G, LPW, true>(p, g, lf, lane, cw, &sc);
+        } else {
+            check_leaf_group<G, LPW>(p, g, lf, lane, cw);
+        }
     }
     cand_flush<G>(p, cw, lane);
     square_ok_flush(p.fin.msd_counters, &sq_sum, cw.q_tail, lane);
-    if (p.fin.done) nice_launch_finish(p.fin, p.out.count);
+    if constexpr (SOUND) {
+        if (sc.pt) rejected_flush(sc.snd->rejected, sc.rej);
+    }
+    if (p.fin.done) nice_launch_finish<SOUND>(p.fin, p.out.count);
 }
 
 // ---------------------------------------------------------------------------
@@ -382,7 +475,8 @@ __device__ __forceinline__ bool common_prefix(u32 (&x)[NW], u32 (&y)[NW], const 
 }
 
 // has_duplicate_msd_prefix (msd_prefix_filter.rs:382-563) on [first, last].
-template <class G>
+// SOUND: without Filter C.
+template <class G, bool SOUND = false>
 __device__ bool msd_skippable(u64 f_lo, u64 f_hi, u64 l_lo, u64 l_hi, const G &g) {
     u32 fn[4] = {(u32)f_lo, (u32)(f_lo >> 32), (u32)f_hi, (u32)(f_hi >> 32)};
     u32 ln[4] = {(u32)l_lo, (u32)(l_lo >> 32), (u32)l_hi, (u32)(l_hi >> 32)};
@@ -398,6 +492,7 @@ __device__ bool msd_skippable(u64 f_lo, u64 f_hi, u64 l_lo, u64 l_hi, const G &g
     if (!common_prefix<12>(fcu, lcu, g, cu)) return false;
     if (cu.dup) return true;
     if (overlaps(sq.mask, cu.mask)) return true;
+    if constexpr (SOUND) return false;
     // Filter C (MSD_LSD_OVERLAP_K_VALUE = 2): first / b^2 == last / b^2, with
     // *first*'s two lowest digits of n^2 and n^3 (msd_prefix_filter.rs:461-559).
     u64 a_lo = f_lo, a_hi = f_hi, b_lo = l_lo, b_hi = l_hi;
@@ -526,10 +621,31 @@ __device__ __forceinline__ u32 block_reserve(u32 *ctr, u32 mine, u32 *slots) {
 
 // The recursion's rule for one node (msd_prefix_filter.rs:583-658):
 // 0 = dropped (has_duplicate_msd_prefix), 1 = leaf, 2 = split in two.
-template <class G, bool TAB = false>
+// SOUND: no Filter C; with the prefix test on a leaf's mask goes to sc->lm --
+// also for the leaves made without a skip test (size <= floor on entry, depth
+// 22), which still count as ranges while every candidate of theirs goes when
+// their prefix repeats.
+template <class G, bool TAB = false, bool SOUND = false>
 __device__ __forceinline__ u32 classify_node(const MsdLaunch &p, u32 level, u64 lo, u64 hi, u64 size,
-                                             const G &g, const uint2 *tab = nullptr) {
+                                             const G &g, const uint2 *tab = nullptr, SoundCtx<SOUND> *sc = nullptr) {
     bool leaf = level >= 22 || size <= p.floor_size;
+    if constexpr (SOUND && IsConst<G>::value) {
+        if (sc->pt) {
+            LeafMask *lm = &sc->lm;
+            *lm = LeafMask{{0, 0, 0}, size > 1 ? 1u : 0u};
+            if (size <= 1) return 1;
+            u64 l_lo = lo, l_hi = hi;
+            add_u128(l_lo, l_hi, size - 1);
+            constexpr int MW = Radix<IsConst<G>::base>::MW;
+            u32 pm[MW];
+            const u32 dup = msd_prefix_masks<IsConst<G>::base, TAB>(lo, hi, l_lo, l_hi, pm, tab);
+#pragma unroll
+            for (int w = 0; w < MW; w++) lm->w[w] = dup ? ~0u : pm[w];
+            if (leaf) return 1;
+            if (dup && !(kProbes && (p.probe & 1))) return 0;
+            return size < 2 * p.floor_size ? 1u : 2u;
+        }
+    }
     if (leaf) return 1;
     u64 l_lo = lo, l_hi = hi;
     add_u128(l_lo, l_hi, size - 1);
@@ -537,10 +653,16 @@ __device__ __forceinline__ u32 classify_node(const MsdLaunch &p, u32 level, u64 
     bool skip = false;
     if (size != 1 && !no_skip_test) {
         if constexpr (IsConst<G>::value) {
-            skip = p.in_range ? msd_skippable_fast<IsConst<G>::base, TAB>(lo, hi, l_lo, l_hi, tab)
-                              : msd_skippable<G>(lo, hi, l_lo, l_hi, g);
+            if constexpr (SOUND) {
+                u32 pm[Radix<IsConst<G>::base>::MW];
+                skip = p.in_range ? msd_prefix_masks<IsConst<G>::base, TAB>(lo, hi, l_lo, l_hi, pm, tab) != 0
+                                  : msd_skippable<G, true>(lo, hi, l_lo, l_hi, g);
+            } else {
+                skip = p.in_range ? msd_skippable_fast<IsConst<G>::base, TAB>(lo, hi, l_lo, l_hi, tab)
+                                  : msd_skippable<G>(lo, hi, l_lo, l_hi, g);
+            }
         } else {
-            skip = msd_skippable<G>(lo, hi, l_lo, l_hi, g);
+            skip = msd_skippable<G, SOUND>(lo, hi, l_lo, l_hi, g);
         }
     }
     if (skip) return 0;
@@ -551,9 +673,12 @@ __device__ __forceinline__ u32 classify_node(const MsdLaunch &p, u32 level, u64 
 // without candidates still counts as an MSD-surviving range, none stored),
 // appended with one atomic per workgroup; statistics accumulated per lane.
 // Every thread of the workgroup calls it (act == 1: this lane has a leaf).
+// masks (sound variants with the prefix test on, else null): the leaf's mask
+// beside each of its records.
 template <u32 MC, bool WIDE>
 __device__ __forceinline__ void append_leaf(const MsdLaunch &p, u32 act, u64 lo, u64 hi, u64 size,
-                                            u32 *slots, u64 &n_st, u64 &c_st, u64 &s_st) {
+                                            u32 *slots, u64 &n_st, u64 &c_st, u64 &s_st,
+                                            LeafMask *masks = nullptr, const LeafMask *lm = nullptr) {
     LeafDesc ld{0, 0, 0, 0};
     if (kProbes && act == 1 && (p.probe & 2)) {
         ld = LeafDesc{lo, hi, size, 0};
@@ -579,6 +704,7 @@ __device__ __forceinline__ void append_leaf(const MsdLaunch &p, u32 act, u64 lo,
             const u64 left = ld.count - (u64)q * kLeafPiece;
             const u32 cnt = left < kLeafPiece ? (u32)left : kLeafPiece;
             p.leaves[pos + q] = Leaf{b0_lo, b0_hi, (u32)gi, cnt};
+            if (masks) masks[pos + q] = *lm;
             gi += cnt;
         }
     }
@@ -608,9 +734,10 @@ __device__ __forceinline__ void flush_stats(const MsdLaunch &p, u64 n_st, u64 c_
     }
 }
 
-template <class G, u32 MC>
+template <class G, u32 MC, class... S>
 __global__ void __launch_bounds__(256)
-msd_level_kernel(MsdLaunch p, u32 level, G g) {
+msd_level_kernel(MsdLaunch p, u32 level, G g, S... snd) {
+    constexpr bool SOUND = sizeof...(S) != 0;
     __shared__ u32 slots[4];
     __shared__ unsigned long long stat[3];
     if (threadIdx.x < 3) stat[threadIdx.x] = 0;
@@ -622,6 +749,7 @@ msd_level_kernel(MsdLaunch p, u32 level, G g) {
     // Workgroup-uniform loop: leaves and children are appended with one atomic
     // per workgroup, statistics summed in LDS and added once at the end.
     const u32 stride = gridDim.x * blockDim.x;
+    [[maybe_unused]] SoundCtx<SOUND> sc = sound_ctx<G>(p.in_range, snd...);
     u64 n_st = 0, c_st = 0, s_st = 0;
     for (u32 b0 = blockIdx.x * blockDim.x; b0 < n_in; b0 += stride) {
         const u32 i = b0 + threadIdx.x;
@@ -631,9 +759,13 @@ msd_level_kernel(MsdLaunch p, u32 level, G g) {
         if (i < n_in) {
             nd = qin[i];
             add_u128(lo, hi, nd.off);
-            act = classify_node(p, level, lo, hi, nd.size, g);
+            if constexpr (SOUND) act = classify_node<G, false, true>(p, level, lo, hi, nd.size, g, nullptr, &sc);
+            else act = classify_node(p, level, lo, hi, nd.size, g);
         }
-        append_leaf<MC, WideN<G>::value>(p, act, lo, hi, nd.size, slots, n_st, c_st, s_st);
+        if constexpr (SOUND)
+            append_leaf<MC, WideN<G>::value>(p, act, lo, hi, nd.size, slots, n_st, c_st, s_st,
+                                             sc.pt ? sc.snd->leaf_masks : nullptr, &sc.lm);
+        else append_leaf<MC, WideN<G>::value>(p, act, lo, hi, nd.size, slots, n_st, c_st, s_st);
         // children
         const u32 cpos = block_reserve(&p.counters[level + 1], act == 2 ? 2u : 0u, slots);
         if (act == 2) {
@@ -657,14 +789,16 @@ msd_level_kernel(MsdLaunch p, u32 level, G g) {
 // beside it, and their grids were sized for the unpruned tree.  Nodes are
 // (offset in the chunk, size) pairs in a per-workgroup ping-pong queue in
 // global memory (`scratch`: gridDim.x x 2 x cap).
-template <class G, u32 MC>
+template <class G, u32 MC, class... S>
 __global__ void __launch_bounds__(256)
-msd_fused_kernel(MsdLaunch p, ChunkNode *scratch, u32 cap, G g) {
+msd_fused_kernel(MsdLaunch p, ChunkNode *scratch, u32 cap, G g, S... snd) {
+    constexpr bool SOUND = sizeof...(S) != 0;
     __shared__ u32 slots[4];
     __shared__ u32 cnt[2];
     __shared__ unsigned long long stat[3];
     if (threadIdx.x < 3) stat[threadIdx.x] = 0;
     ChunkNode *qa = scratch + (u64)blockIdx.x * 2 * cap, *qb = qa + cap;
+    [[maybe_unused]] SoundCtx<SOUND> sc = sound_ctx<G>(p.in_range, snd...);
     u64 n_st = 0, c_st = 0, s_st = 0;
     for (u64 ci = blockIdx.x; ci < p.nchunks; ci += gridDim.x) {
         const u64 c = p.deal_offset + (p.first + ci) * p.deal_stride;
@@ -691,9 +825,14 @@ msd_fused_kernel(MsdLaunch p, ChunkNode *scratch, u32 cap, G g) {
                 if (i < n_in) {
                     nd = qin[i];
                     add_u128(lo, hi, nd.off);
-                    act = classify_node(p, level, lo, hi, nd.size, g);
+                    if constexpr (SOUND)
+                        act = classify_node<G, false, true>(p, level, lo, hi, nd.size, g, nullptr, &sc);
+                    else act = classify_node(p, level, lo, hi, nd.size, g);
                 }
-                append_leaf<MC, WideN<G>::value>(p, act, lo, hi, nd.size, slots, n_st, c_st, s_st);
+                if constexpr (SOUND)
+                    append_leaf<MC, WideN<G>::value>(p, act, lo, hi, nd.size, slots, n_st, c_st, s_st,
+                                                     sc.pt ? sc.snd->leaf_masks : nullptr, &sc.lm);
+                else append_leaf<MC, WideN<G>::value>(p, act, lo, hi, nd.size, slots, n_st, c_st, s_st);
                 if (act == 2) {
                     const u32 cp = atomicAdd(&cnt[1], 2u);
                     if (cp + 2 > cap) {
@@ -772,10 +911,28 @@ constexpr u32 kWalkQ = 256;
 // workgroup passes 80 KB and only one fits a CU, so its queue is half as long.
 template <class G>
 constexpr u32 walk_q() { return PairTab<G>::N * 8 + 8 * (kCubeQ + kWalkQ) * 16 + 512 <= 80 * 1024 ? kWalkQ : kWalkQ / 2; }
+// Sound variants: a queued leaf also holds its 8-byte prefix mask (24 bytes),
+// which leaves 256 entries only to b40..45; the others walk 128, as b64 does
+// anyway, and two workgroups still fit a CU.
+template <class G>
+constexpr u32 walk_q_sound() {
+    return PairTab<G>::N * 8 + 8 * (kCubeQ * 16 + kWalkQ * 24) + 512 <= 80 * 1024 ? kWalkQ : kWalkQ / 2;
+}
+// LDS of a sound variant only (a block-scope array would also grow the
+// reference filter's instantiations).
+template <class T, u32 N>
+__device__ __forceinline__ T *lds_array() {
+    __shared__ T a[N];
+    return a;
+}
 
-template <int B, bool WIDE, u32 Q = kWalkQ>
+// SOUND: bit 31 of a leaf's count says it holds >= 2 numbers; with the prefix
+// test on, qm holds the queued leaves' prefix masks and a lane steps its
+// residue index past the candidates the test rejects (counted in sc->rej)
+// before it joins the round, so the square test runs on survivors only.
+template <int B, bool WIDE, u32 Q = kWalkQ, bool SOUND = false>
 __device__ __forceinline__ void walk_leaves(const NiceonlyLaunch &c, const LeafW *q, u32 head, u32 n, u32 lane,
-                                            CandWave &cw) {
+                                            CandWave &cw, SoundCtx<SOUND> *sc = nullptr, const uint2 *qm = nullptr) {
     wave_sync_lds();  // queue entries written by other lanes
     u32 taken = 0;    // wave-uniform
     bool have = false;
@@ -795,6 +952,15 @@ __device__ __forceinline__ void walk_leaves(const NiceonlyLaunch &c, const LeafW
                     idx &= (1u << kWideG0Bits) - 1;
                 }
                 left = e.count;
+                if constexpr (SOUND) {
+                    sc->lm.multi = left >> 31;
+                    left &= 0x7fffffffu;
+                    if (sc->pt) {
+                        const uint2 m = qm[(head + taken + r) & (Q - 1)];
+                        sc->lm.w[0] = m.x;
+                        sc->lm.w[1] = m.y;
+                    }
+                }
                 if (idx >= c.R) {  // g0 == R: the first candidate is in the next cycle
                     idx -= c.R;
                     cb += c.M;
@@ -804,6 +970,20 @@ __device__ __forceinline__ void walk_leaves(const NiceonlyLaunch &c, const LeafW
             }
             const u32 np = (u32)__popcll(need);
             taken = n - taken > np ? taken + np : n;
+        }
+        if constexpr (SOUND) {
+            if (sc->pt) {
+                const u32 pm[2] = {sc->lm.w[0], sc->lm.w[1]};
+                while (have && cand_rejected<B>(*sc->snd, pm, sc->lm.multi, idx)) {
+                    sc->rej++;
+                    if (++idx == c.R) {
+                        idx = 0;
+                        cb += c.M;
+                        if constexpr (WIDE) cbh += cb < c.M ? 1u : 0u;
+                    }
+                    have = --left != 0;
+                }
+            }
         }
         if (!__ballot(have)) {
             if (taken >= n) break;
@@ -849,14 +1029,15 @@ constexpr int wave_occupancy() {
     return IsConst<G>::value && IsConst<G>::base > 64 ? 2 : (WideN<G>::value ? NICE_WIDE_WAVES : 4);
 }
 
-template <class G, u32 MC>
+template <class G, u32 MC, class... S>
 __global__ void __launch_bounds__(kWaveWG) __attribute__((amdgpu_waves_per_eu(wave_occupancy<G>())))
-msd_wave_kernel(MsdLaunch p, NiceonlyLaunch c, u32 level0, StackNode *scratch, G g) {
+msd_wave_kernel(MsdLaunch p, NiceonlyLaunch c, u32 level0, StackNode *scratch, G g, S... snd) {
+    constexpr bool SOUND = sizeof...(S) != 0;
     constexpr u32 W = kWaveWG / 64;
     constexpr bool WALK = PairTab<G>::on && MC != 0;  // lane walk (see walk_leaves)
     constexpr bool WIDE = WALK && WideN<G>::value;
     // (a round queues <= 64 leaves on top of fewer than kWalkAt: 192 of 256, b64 64 of 128)
-    constexpr u32 kWalkQ = walk_q<G>(), kWalkAt = kWalkQ - 64;
+    constexpr u32 kWalkQ = SOUND ? walk_q_sound<G>() : walk_q<G>(), kWalkAt = kWalkQ - 64;
     __shared__ ulonglong2 cq[W][IsConst<G>::value ? kCubeQ : 1];
     __shared__ Leaf lq[W][WALK ? 1 : kLeafQ];
     __shared__ LeafW lw[W][WALK ? kWalkQ : 1];
@@ -873,6 +1054,12 @@ msd_wave_kernel(MsdLaunch p, NiceonlyLaunch c, u32 level0, StackNode *scratch, G
     LeafW *qw = lw[wv];
     CandWave cw = cand_wave(c, cq[wv], tab);
     u64 n_st = 0, c_st = 0, s_st = 0;
+    // SOUND: the queued leaves' prefix masks beside lw / lq
+    [[maybe_unused]] SoundCtx<SOUND> sc = sound_ctx<G>(p.in_range, snd...);
+    [[maybe_unused]] uint2 *qwm = nullptr;
+    [[maybe_unused]] LeafMask *qm = nullptr;
+    if constexpr (SOUND && WALK) qwm = lds_array<uint2, W * kWalkQ>() + wv * kWalkQ;
+    else if constexpr (SOUND) qm = lds_array<LeafMask, W * kLeafQ>() + wv * kLeafQ;
 
     // Leaves the BFS levels above produced (clipped or depth-limited nodes):
     // already stride descriptors in the batch's leaf list.
@@ -880,7 +1067,13 @@ msd_wave_kernel(MsdLaunch p, NiceonlyLaunch c, u32 level0, StackNode *scratch, G
     for (u64 b = gwave * kLeafGroup; b < n_list; b += nwaves * kLeafGroup) {
         Leaf lf{0, 0, 0, 0};
         if (lane < kLeafGroup && b + lane < n_list) lf = p.leaves[b + lane];
-        check_leaf_group<G, kLeafGroup>(c, g, lf, lane, cw);
+        if constexpr (SOUND) {
+            sc.lm = LeafMask{{0, 0, 0}, 0};
+            if (sc.pt && lane < kLeafGroup && b + lane < n_list) sc.lm = sc.snd->leaf_masks[b + lane];
+            check_leaf_group<G, kLeafGroup, true>(c, g, lf, lane, cw, &sc);
+        } else {
+            check_leaf_group<G, kLeafGroup>(c, g, lf, lane, cw);
+        }
     }
 
     const MsdNode *roots = p.q[level0 & 1];
@@ -909,7 +1102,7 @@ msd_wave_kernel(MsdLaunch p, NiceonlyLaunch c, u32 level0, StackNode *scratch, G
         wave_sync_global();  // popped before the pushes below reuse the slots
         u64 lo = p.start_lo, hi = p.start_hi;
         add_u128(lo, hi, nd.off);
-        const u32 act = lane < cnt ? classify_node<G, PairTab<G>::on>(p, nd.depth, lo, hi, nd.size, g, tab) : 0u;
+        const u32 act = lane < cnt ? classify_node<G, PairTab<G>::on, SOUND>(p, nd.depth, lo, hi, nd.size, g, tab, &sc) : 0u;
         // a leaf: its stride descriptor to the queue (statistics as the
         // reference counts them: every MSD-surviving range)
         LeafDesc ld{0, 0, 0, 0};
@@ -922,6 +1115,15 @@ msd_wave_kernel(MsdLaunch p, NiceonlyLaunch c, u32 level0, StackNode *scratch, G
         const bool put = act == 1 && ld.count != 0 && !(kProbes && (p.probe & 4));  // probe 4: MSD only
         const u64 bl = __ballot(put);
         if (put) {
+            if constexpr (SOUND) {
+                // bit 31 of a walk entry's count: the leaf holds >= 2 numbers
+                if constexpr (WALK) {
+                    ld.count |= sc.pt ? sc.lm.multi << 31 : 0u;
+                    qwm[(lq_tail + lane_rank(bl)) & (kWalkQ - 1)] = make_uint2(sc.lm.w[0], sc.lm.w[1]);
+                } else {
+                    qm[(lq_tail + lane_rank(bl)) & (kLeafQ - 1)] = sc.lm;
+                }
+            }
             if constexpr (WIDE)
                 qw[(lq_tail + lane_rank(bl)) & (kWalkQ - 1)] =
                     LeafW{ld.b0_lo, ld.g0 | (u32)ld.b0_hi << kWideG0Bits, (u32)ld.count};
@@ -947,7 +1149,9 @@ msd_wave_kernel(MsdLaunch p, NiceonlyLaunch c, u32 level0, StackNode *scratch, G
         // at a time in packed groups
         if constexpr (WALK) {
             if (lq_tail - lq_head >= kWalkAt) {
-                walk_leaves<IsConst<G>::base, WIDE, kWalkQ>(c, qw, lq_head, lq_tail - lq_head, lane, cw);
+                if constexpr (SOUND)
+                    walk_leaves<IsConst<G>::base, WIDE, kWalkQ, true>(c, qw, lq_head, lq_tail - lq_head, lane, cw, &sc, qwm);
+                else walk_leaves<IsConst<G>::base, WIDE, kWalkQ>(c, qw, lq_head, lq_tail - lq_head, lane, cw);
                 lq_head = lq_tail;
             }
         } else if (lq_tail - lq_head >= 64) {
@@ -955,34 +1159,53 @@ msd_wave_kernel(MsdLaunch p, NiceonlyLaunch c, u32 level0, StackNode *scratch, G
             for (u32 gq = 0; gq < 64; gq += kLeafGroup) {
                 Leaf lf{0, 0, 0, 0};
                 if (lane < kLeafGroup) lf = q[(lq_head + gq + lane) & (kLeafQ - 1)];
-                check_leaf_group<G, kLeafGroup>(c, g, lf, lane, cw);
+                if constexpr (SOUND) {
+                    if (lane < kLeafGroup) sc.lm = qm[(lq_head + gq + lane) & (kLeafQ - 1)];
+                    check_leaf_group<G, kLeafGroup, true>(c, g, lf, lane, cw, &sc);
+                } else {
+                    check_leaf_group<G, kLeafGroup>(c, g, lf, lane, cw);
+                }
             }
             lq_head += 64;
         }
     }
     wave_sync_lds();
     if constexpr (WALK) {
-        if (lq_head != lq_tail) walk_leaves<IsConst<G>::base, WIDE, kWalkQ>(c, qw, lq_head, lq_tail - lq_head, lane, cw);
+        if constexpr (SOUND) {
+            if (lq_head != lq_tail)
+                walk_leaves<IsConst<G>::base, WIDE, kWalkQ, true>(c, qw, lq_head, lq_tail - lq_head, lane, cw, &sc, qwm);
+        } else {
+            if (lq_head != lq_tail) walk_leaves<IsConst<G>::base, WIDE, kWalkQ>(c, qw, lq_head, lq_tail - lq_head, lane, cw);
+        }
         lq_head = lq_tail;
     }
     while (lq_head != lq_tail) {
         const u32 n = lq_tail - lq_head < kLeafGroup ? lq_tail - lq_head : kLeafGroup;
         Leaf lf{0, 0, 0, 0};
         if (lane < n) lf = q[(lq_head + lane) & (kLeafQ - 1)];
-        check_leaf_group<G, kLeafGroup>(c, g, lf, lane, cw);
+        if constexpr (SOUND) {
+            if (lane < n) sc.lm = qm[(lq_head + lane) & (kLeafQ - 1)];
+            check_leaf_group<G, kLeafGroup, true>(c, g, lf, lane, cw, &sc);
+        } else {
+            check_leaf_group<G, kLeafGroup>(c, g, lf, lane, cw);
+        }
         lq_head += n;
     }
     cand_flush<G>(c, cw, lane);
     square_ok_flush(c.fin.msd_counters, &sq_sum, cw.q_tail, lane);
     flush_stats(p, n_st, c_st, s_st, stat);
-    if (c.fin.done) nice_launch_finish(c.fin, c.out.count);
+    if constexpr (SOUND) {
+        if (sc.pt) rejected_flush(sc.snd->rejected, sc.rej);
+    }
+    if (c.fin.done) nice_launch_finish<SOUND>(c.fin, c.out.count);
 }
 
 // ---------------------------------------------------------------------------
 // Host launchers
 // ---------------------------------------------------------------------------
-template <class G>
-static hipError_t launch_nice(const NiceonlyLaunch &p, const G &g, int num_cus, hipStream_t s) {
+// (S: nothing, or one SoundLaunch for the sound variants)
+template <class G, class... S>
+static hipError_t launch_nice(const NiceonlyLaunch &p, const G &g, int num_cus, hipStream_t s, S... snd) {
     u64 waves = p.n_leaves_dev ? (u64)num_cus * 32 : ((u64)p.n_leaves + 7) / 8;
     u64 grid = (waves + 3) / 4;
     // (probe NICE_NICE_GRID: caps of 128..2048 workgroups tie on the bench
@@ -990,7 +1213,7 @@ static hipError_t launch_nice(const NiceonlyLaunch &p, const G &g, int num_cus, 
     const u64 cap = probe_knob("NICE_NICE_GRID", (u64)num_cus * 8);
     if (grid > cap) grid = cap;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(niceonly_kernel<G>, dim3((u32)grid), dim3(256), 0, s, p, g);
+    hipLaunchKernelGGL((niceonly_kernel<G, S...>), dim3((u32)grid), dim3(256), 0, s, p, g, snd...);
     return hipGetLastError();
 }
 
@@ -998,8 +1221,8 @@ static hipError_t launch_nice(const NiceonlyLaunch &p, const G &g, int num_cus, 
 // into p.q[0], the batch's counters zeroed.
 void launch_msd_init(const MsdLaunch &p, hipStream_t s);
 
-template <class G, u32 MC = 0>
-static hipError_t launch_msd(const MsdLaunch &p, const G &g, int num_cus, hipStream_t s) {
+template <class G, u32 MC = 0, class... S>
+static hipError_t launch_msd(const MsdLaunch &p, const G &g, int num_cus, hipStream_t s, S... snd) {
     launch_msd_init(p, s);
     const u64 nchunks = p.nchunks;
     // A node of level d has at most ceil(chunk / 2^d) numbers and splits only
@@ -1015,7 +1238,7 @@ static hipError_t launch_msd(const MsdLaunch &p, const G &g, int num_cus, hipStr
         u64 grid = (nodes + 255) / 256;
         const u64 cap = (u64)num_cus * 2;
         if (grid > cap || nodes >> level != nchunks) grid = cap;
-        hipLaunchKernelGGL((msd_level_kernel<G, MC>), dim3((u32)grid), dim3(256), 0, s, p, level, g);
+        hipLaunchKernelGGL((msd_level_kernel<G, MC, S...>), dim3((u32)grid), dim3(256), 0, s, p, level, g, snd...);
     }
     return hipGetLastError();
 }
@@ -1025,25 +1248,25 @@ static hipError_t launch_msd(const MsdLaunch &p, const G &g, int num_cus, hipStr
 // pipelined step was 1.3 % faster; on the whole 1e9 field 0.7 % slower (the
 // niceonly chain 0.061 against 0.040 ms) and on the 8-way dealt shares, the
 // N = 8 load, 0.7-0.9 % slower; profiles/r06/niceonly/msd_wg.log, sp_wg.log.)
-template <class G, u32 MC = 0>
+template <class G, u32 MC = 0, class... S>
 static hipError_t launch_fused(const MsdLaunch &p, const G &g, ChunkNode *scratch, u32 cap, u32 grid,
-                               hipStream_t s) {
-    hipLaunchKernelGGL((msd_fused_kernel<G, MC>), dim3(grid), dim3(256), 0, s, p, scratch, cap, g);
+                               hipStream_t s, S... snd) {
+    hipLaunchKernelGGL((msd_fused_kernel<G, MC, S...>), dim3(grid), dim3(256), 0, s, p, scratch, cap, g, snd...);
     return hipGetLastError();
 }
 
-template <class G, u32 MC = 0>
+template <class G, u32 MC = 0, class... S>
 static hipError_t launch_wave(const MsdLaunch &p, const NiceonlyLaunch &c, u32 level0, StackNode *scratch,
-                              u32 grid, const G &g, int num_cus, hipStream_t s) {
+                              u32 grid, const G &g, int num_cus, hipStream_t s, S... snd) {
     launch_msd_init(p, s);
     for (u32 level = 0; level < level0; level++) {
         const u64 nodes = p.nchunks << level;
         u64 lgrid = (nodes + 255) / 256;
         const u64 cap = (u64)num_cus * 2;
         if (lgrid > cap) lgrid = cap;
-        hipLaunchKernelGGL((msd_level_kernel<G, MC>), dim3((u32)lgrid), dim3(256), 0, s, p, level, g);
+        hipLaunchKernelGGL((msd_level_kernel<G, MC, S...>), dim3((u32)lgrid), dim3(256), 0, s, p, level, g, snd...);
     }
-    hipLaunchKernelGGL((msd_wave_kernel<G, MC>), dim3(grid), dim3(kWaveWG), 0, s, p, c, level0, scratch, g);
+    hipLaunchKernelGGL((msd_wave_kernel<G, MC, S...>), dim3(grid), dim3(kWaveWG), 0, s, p, c, level0, scratch, g, snd...);
     return hipGetLastError();
 }
 
@@ -1064,6 +1287,15 @@ struct BaseLaunch {
     static hipError_t msd(const MsdLaunch &p, int num_cus, hipStream_t s, ChunkNode *scratch, u32 cap, u32 grid);
     static hipError_t wave(const MsdLaunch &p, const NiceonlyLaunch &c, u32 level0, StackNode *scratch, u32 grid,
                            int num_cus, hipStream_t s);
+    // The sound variants, for the fields they run the prefix test on
+    // (sound_fast: in range on the k = 2 table); niceonly.hip sends every other
+    // sound field to the run-time-base variants.
+    static bool sound_fast(const MsdLaunch &p);
+    static hipError_t nice_sound(const NiceonlyLaunch &p, int num_cus, hipStream_t s, const SoundLaunch &snd);
+    static hipError_t msd_sound(const MsdLaunch &p, int num_cus, hipStream_t s, ChunkNode *scratch, u32 cap, u32 grid,
+                                const SoundLaunch &snd);
+    static hipError_t wave_sound(const MsdLaunch &p, const NiceonlyLaunch &c, u32 level0, StackNode *scratch,
+                                 u32 grid, int num_cus, hipStream_t s, const SoundLaunch &snd);
     static hipError_t unique(const u64 *n_pairs, u32 count, u32 *out, hipStream_t s);
 };
 

@@ -50,6 +50,34 @@ hipError_t BaseLaunch<B>::wave(const MsdLaunch &p, const NiceonlyLaunch &c, u32 
     return launch_wave(p, c, level0, scratch, grid, ConstBase<B>{}, num_cus, s);
 }
 
+// Sound variants: one instantiation set per base -- the const-modulus one of a
+// two-word base, the plain one of a three-word base.
+template <int B>
+bool BaseLaunch<B>::sound_fast(const MsdLaunch &p) {
+    if (!p.in_range || p.M != (u32)(B - 1) * B * B) return false;
+    return const_modulus<B>() == 0 || const_mod_field<B>(p);
+}
+
+template <int B>
+hipError_t BaseLaunch<B>::nice_sound(const NiceonlyLaunch &p, int num_cus, hipStream_t s, const SoundLaunch &snd) {
+    return launch_nice<ConstBase<B>>(p, ConstBase<B>{}, num_cus, s, snd);
+}
+
+template <int B>
+hipError_t BaseLaunch<B>::msd_sound(const MsdLaunch &p, int num_cus, hipStream_t s, ChunkNode *scratch, u32 cap,
+                                    u32 grid, const SoundLaunch &snd) {
+    constexpr u32 MC = const_modulus<B>();
+    if (scratch) return launch_fused<ConstBase<B>, MC>(p, ConstBase<B>{}, scratch, cap, grid, s, snd);
+    return launch_msd<ConstBase<B>, MC>(p, ConstBase<B>{}, num_cus, s, snd);
+}
+
+template <int B>
+hipError_t BaseLaunch<B>::wave_sound(const MsdLaunch &p, const NiceonlyLaunch &c, u32 level0, StackNode *scratch,
+                                     u32 grid, int num_cus, hipStream_t s, const SoundLaunch &snd) {
+    return launch_wave<ConstBase<B>, const_modulus<B>()>(p, c, level0, scratch, grid, ConstBase<B>{}, num_cus, s,
+                                                               snd);
+}
+
 template <int B>
 hipError_t BaseLaunch<B>::unique(const u64 *n_pairs, u32 count, u32 *out, hipStream_t s) {
     hipLaunchKernelGGL(unique_fast_kernel<B>, dim3((count + 255) / 256), dim3(256), 0, s, n_pairs, count, out);

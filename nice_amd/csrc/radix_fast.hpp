@@ -399,4 +399,51 @@ __host__ __device__ __forceinline__ bool msd_skippable_fast(u64 f_lo, u64 f_hi, 
     return false;
 }
 
+// ---------------------------------------------------------------------------
+// Sound filter (NICE_FILTER_SOUND): has_duplicate_msd_prefix without Filter C,
+// and the per-candidate prefix test that replaces it.
+//
+// Every n of a leaf [first, last] carries the leaf's common leading digits of
+// n^2 (P2) and n^3 (P3), and its two lowest digits of n^2 and n^3 (L) depend
+// only on n mod b^2, which a k >= 2 stride residue fixes.  n is rejected iff
+// the list P2 + P3 + L holds a repeated value; a leaf of one number rejects
+// nothing.  A leaf carries the digit mask of P2 + P3 (all ones when P2 + P3
+// itself repeats: every candidate goes) and whether it holds >= 2 numbers; a
+// residue carries the digit mask of L and whether L itself repeats.
+// ---------------------------------------------------------------------------
+
+// The square / cube / overlap checks of msd_skippable_fast on [first, last]
+// (both in range): non-zero when they skip the range, else pm = the digit mask
+// of P2 + P3.
+template <int BASE, bool TAB = false>
+__host__ __device__ __forceinline__ u32 msd_prefix_masks(u64 f_lo, u64 f_hi, u64 l_lo, u64 l_hi,
+                                                         u32 (&pm)[Radix<BASE>::MW], const uint2 *tab = nullptr) {
+    using R = Radix<BASE>;
+    u32 Xf[R::NX], Xl[R::NX], Sf[R::NS], Sl[R::NS];
+    to_limbs<BASE>(f_lo, f_hi, Xf);
+    to_limbs<BASE>(l_lo, l_hi, Xl);
+    square_limbs<BASE>(Xf, Sf);
+    square_limbs<BASE>(Xl, Sl);
+    u32 msq[R::MW], dsq;
+    if constexpr (TAB) msd_prefix_tab<BASE>(Sf, Sl, R::D2, msq, dsq, tab);
+    else msd_prefix<BASE>(Sf, Sl, R::D2, msq, dsq);
+    u32 Cf[R::NC], Cl[R::NC];
+    cube_limbs<BASE>(Sf, Xf, Cf);
+    cube_limbs<BASE>(Sl, Xl, Cl);
+    u32 mcu[R::MW], dcu;
+    if constexpr (TAB) msd_prefix_tab<BASE>(Cf, Cl, R::D3, mcu, dcu, tab);
+    else msd_prefix<BASE>(Cf, Cl, R::D3, mcu, dcu);
+#pragma unroll
+    for (int w = 0; w < R::MW; w++) pm[w] = msq[w] | mcu[w];
+    return dsq | dcu | (moverlap(msq, mcu) ? 1u : 0u);
+}
+
+// The rejection rule on (leaf mask, leaf holds >= 2 numbers, residue mask,
+// residue's L repeats).
+template <int MW>
+__host__ __device__ __forceinline__ bool prefix_rejects(const u32 (&pm)[MW], u32 multi, const u32 (&low)[MW],
+                                                        u32 low_dup) {
+    return moverlap(pm, low) || (multi && low_dup);
+}
+
 }  // namespace nice
