@@ -357,6 +357,54 @@ int nice_check_prefix_reject_inrange(uint32_t base, uint64_t start_lo, uint64_t 
  * (lo, hi) pairs, returns the count via *n_out.  Bases without an FD kernel: 0. */
 int nice_fd_segment_cuts(uint32_t base, uint64_t *out, size_t cap, size_t *n_out);
 
+/* Batched detailed ranges: many (small) ranges in one call.  `bounds` holds
+ * four u64 per range -- start_lo, start_hi, end_lo, end_hi, the layout
+ * nice_msd_valid_ranges writes, so its output can be passed straight in.
+ * Ranges inside the valid range of a base with an FD kernel run together: one
+ * kernel launch per limb layout present, each workgroup working for one range
+ * and adding to that range's own histogram row.  Every other range (a base
+ * without an FD kernel, a range outside the base's valid range or across one
+ * of its ends; also a range of more than 2^28 numbers, which fills the GPU as
+ * a field of its own) runs through nice_process_range_detailed's path inside
+ * the call and is counted in nice_ranges_stats.fallback_ranges.
+ *   NICE_RANGES_PER_RANGE: hist receives n_ranges rows of base + 1 u64; row i
+ *     is, bin for bin, nice_process_range_detailed's histogram of range i.
+ *   NICE_RANGES_SUM: hist receives one row, the sum over the ranges.
+ * The list is the concatenation, in range order, of each range's near-misses
+ * in ascending order; out_range[j] (may be null) is entry j's range index.
+ * Ranges may overlap or repeat: each gets its own complete answer.  Every row
+ * passes nice_validate_detailed before the call returns.
+ * Errors: NICE_ERR_INVALID (n_ranges 0 or above 2^20, an empty or inverted
+ * range -- the message names its index --, base outside 2..128),
+ * NICE_ERR_CAPACITY (*n_out = the needed length; the results are kept, and
+ * the same call with room returns them without running again).
+ * The call has its own stream and buffers per device and its own lock: it
+ * takes no detailed slot for the batched ranges and does not wait for fields
+ * in flight. */
+#define NICE_RANGES_PER_RANGE 0
+#define NICE_RANGES_SUM 1
+int nice_process_ranges_detailed(nice_ctx *ctx, uint32_t base, const uint64_t *bounds,
+                                 size_t n_ranges, uint32_t flags, uint64_t *hist,
+                                 nice_number *out, uint32_t *out_range, size_t cap,
+                                 size_t *n_out);
+typedef struct {
+    uint32_t launches;        /* batch-kernel launches of the last call */
+    uint32_t fallback_ranges; /* ranges run by the per-field path */
+    uint64_t numbers;
+    double kernel_ms;         /* HIP events around the batch launches */
+} nice_ranges_stats;
+int nice_last_ranges_stats(nice_ctx *ctx, nice_ranges_stats *out);
+/* The same on the host cores (no device): loops nice_cpu_process_range_detailed. */
+int nice_cpu_process_ranges_detailed(uint32_t base, const uint64_t *bounds, size_t n_ranges,
+                                     uint32_t flags, int32_t threads, uint64_t *hist,
+                                     nice_number *out, uint32_t *out_range, size_t cap,
+                                     size_t *n_out);
+/* Test hook (no device): the batch plan of nice_process_ranges_detailed for in-range
+ * ranges of an FD base.  Writes 6 u64 per workgroup: start_lo, start_hi, lanes, chunk,
+ * range index, combo index.  *n_out = the true count. */
+int nice_debug_ranges_plan(uint32_t base, const uint64_t *bounds, size_t n_ranges,
+                           uint64_t *units, size_t cap, size_t *n_out);
+
 /* Diagnostics: per-n results of the device functions the kernels use. */
 int nice_debug_unique_counts(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t count,
                              uint32_t base, uint32_t *out);

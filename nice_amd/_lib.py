@@ -28,6 +28,9 @@ NICE_MSD_FLOOR_ADAPTIVE = (1 << 64) - 1  # msd_floor: the reference GPU path's A
 # (no Filter C; a per-candidate prefix test instead, see include/nice_hip.h)
 NICE_FILTER_REFERENCE = 0
 NICE_FILTER_SOUND = 1
+# nice_process_ranges_detailed flags: one histogram row per range, or their sum
+NICE_RANGES_PER_RANGE = 0
+NICE_RANGES_SUM = 1
 
 # Every symbol include/nice_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -45,6 +48,8 @@ EXPORTS = (
     "nice_host_threads", "nice_debug_cgroup_cpus", "nice_debug_force_sib_stride",
     "nice_niceonly_prefix_rejected", "nice_msd_valid_ranges_ex", "nice_cpu_process_range_niceonly_ex",
     "nice_check_prefix_reject_inrange",
+    "nice_process_ranges_detailed", "nice_last_ranges_stats", "nice_cpu_process_ranges_detailed",
+    "nice_debug_ranges_plan",
 )
 
 
@@ -82,6 +87,11 @@ class nice_kernel_stats(ctypes.Structure):
     _fields_ = [("kernel_ms", ctypes.c_double), ("launches", ctypes.c_uint32),
                 ("fd_kernel", ctypes.c_uint32), ("numbers", ctypes.c_uint64),
                 ("sib_lanes", ctypes.c_uint32), ("sib_stride", ctypes.c_uint32)]
+
+
+class nice_ranges_stats(ctypes.Structure):
+    _fields_ = [("launches", ctypes.c_uint32), ("fallback_ranges", ctypes.c_uint32),
+                ("numbers", ctypes.c_uint64), ("kernel_ms", ctypes.c_double)]
 
 
 _lib = None
@@ -157,6 +167,10 @@ def lib():
         "nice_host_threads": ([], u32),
         "nice_debug_cgroup_cpus": ([ctypes.c_char_p, ctypes.c_char_p], u32),
         "nice_debug_force_sib_stride": ([u32], i32),
+        "nice_process_ranges_detailed": ([vp, u32, P64, sz, u32, P64, PN, P32, sz, PSZ], i32),
+        "nice_last_ranges_stats": ([vp, ctypes.POINTER(nice_ranges_stats)], i32),
+        "nice_cpu_process_ranges_detailed": ([u32, P64, sz, u32, i32, P64, PN, P32, sz, PSZ], i32),
+        "nice_debug_ranges_plan": ([u32, P64, sz, P64, sz, PSZ], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

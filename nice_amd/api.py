@@ -9,6 +9,7 @@ north star asks for).  All compute happens in libnice_hip.so.
 """
 from __future__ import annotations
 
+import array
 import ctypes
 import threading
 from dataclasses import dataclass
@@ -174,6 +175,35 @@ class KernelStats:
     sib_stride: int = 0  # ... and its lane stride
 
 
+@dataclass
+class RangesStats:
+    launches: int         # batch-kernel launches of the call
+    fallback_ranges: int  # ranges run one by one as fields (not inside an FD base's valid range)
+    numbers: int
+    kernel_ms: float      # HIP events around the batch launches
+
+
+def _pack_ranges(ranges):
+    """(start, end) pairs or FieldSize -> the four-u64-per-range bounds array
+    nice_msd_valid_ranges writes."""
+    pairs = [(r.range_start, r.range_end) if isinstance(r, FieldSize) else (int(r[0]), int(r[1]))
+             for r in ranges]
+    if any(s < 0 or e < 0 or s >> 128 or e >> 128 for s, e in pairs):
+        raise ValueError("value must fit in u128")
+    flat = array.array("Q", [x for s, e in pairs for x in (s & MASK64, s >> 64, e & MASK64, e >> 64)])
+    if not pairs:
+        flat = array.array("Q", [0, 0, 0, 0])
+    # (one buffer copy: filling a ctypes array element by element costs ~1 us per value)
+    return (ctypes.c_uint64 * len(flat)).from_buffer_copy(flat), len(pairs)
+
+
+def _ranges_result(hist, nb, nrows, out, idx, n):
+    full = memoryview(hist).cast("B").cast("Q").tolist()
+    rows = [full[i * nb:(i + 1) * nb] for i in range(nrows)]
+    return rows, [(out[i].number_lo | (out[i].number_hi << 64), out[i].num_uniques, idx[i])
+                  for i in range(n)]
+
+
 class GpuContext:
     """GpuContext (client_process_gpu.rs:196-306).  `devices` extends the
     reference's single ordinal: a field is sharded across the listed GPUs."""
@@ -270,6 +300,35 @@ class GpuContext:
             check(rc)
             return list(hist), [(out[i].number_lo | (out[i].number_hi << 64), out[i].num_uniques)
                                 for i in range(n.value)]
+
+    # -- batched detailed ranges ------------------------------------------------
+    def detailed_ranges(self, ranges, base: int, sum: bool = False, cap: int = 0):
+        """Many (small) ranges in one call (nice_process_ranges_detailed):
+        `ranges` holds (start, end) pairs or FieldSize.  Returns (rows,
+        [(n, u, range_index)]): rows[i] is range i's histogram (base+1 bins) --
+        with sum=True one row, the sum over the ranges -- and the list is each
+        range's near-misses ascending, in range order.  In-range ranges of an
+        FD base share one kernel launch per limb layout; see ranges_stats()."""
+        bounds, n_ranges = _pack_ranges(ranges)
+        nb = base + 1
+        hist = (ctypes.c_uint64 * (nb * (1 if sum else max(n_ranges, 1))))()
+        flags = _lib.NICE_RANGES_SUM if sum else _lib.NICE_RANGES_PER_RANGE
+        cap = max(cap, 1024)
+        while True:
+            out, idx, n = _cpu_out(cap), (ctypes.c_uint32 * cap)(), ctypes.c_size_t()
+            rc = lib().nice_process_ranges_detailed(self._h, base, bounds, n_ranges, flags, hist, out, idx,
+                                                    cap, n)
+            if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
+                cap = n.value
+                continue
+            check(rc)
+            return _ranges_result(hist, nb, 1 if sum else n_ranges, out, idx, n.value)
+
+    def ranges_stats(self) -> "RangesStats":
+        """Statistics of this context's last detailed_ranges call."""
+        s = _lib.nice_ranges_stats()
+        check(lib().nice_last_ranges_stats(self._h, s))
+        return RangesStats(s.launches, s.fallback_ranges, s.numbers, s.kernel_ms)
 
     # -- niceonly -------------------------------------------------------------
     def niceonly_raw(self, start: int, end: int, base: int, msd_floor: int = 0,
@@ -521,6 +580,44 @@ def process_range_detailed_cpu(range_: FieldSize, base: int, threads: int = 1) -
         distribution=[UniquesDistributionSimple(i, hist[i]) for i in range(1, base + 1)],
         nice_numbers=[NiceNumberSimple(out[i].number_lo | (out[i].number_hi << 64), out[i].num_uniques)
                       for i in range(n.value)])
+
+
+def detailed_ranges_cpu(ranges, base: int, sum: bool = False, threads: int = 1):
+    """GpuContext.detailed_ranges on the host cores
+    (nice_cpu_process_ranges_detailed): no device."""
+    bounds, n_ranges = _pack_ranges(ranges)
+    nb = base + 1
+    hist = (ctypes.c_uint64 * (nb * (1 if sum else max(n_ranges, 1))))()
+    flags = _lib.NICE_RANGES_SUM if sum else _lib.NICE_RANGES_PER_RANGE
+    cap = 1024
+    while True:
+        out, idx, n = _cpu_out(cap), (ctypes.c_uint32 * cap)(), ctypes.c_size_t()
+        rc = lib().nice_cpu_process_ranges_detailed(base, bounds, n_ranges, flags, threads, hist, out, idx,
+                                                     cap, n)
+        if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
+            cap = n.value
+            continue
+        check(rc)
+        return _ranges_result(hist, nb, 1 if sum else n_ranges, out, idx, n.value)
+
+
+def _ranges_field_results(rows, lst, base: int) -> List[FieldResults]:
+    per = [[] for _ in rows]
+    for n, u, i in lst:
+        per[i].append(NiceNumberSimple(n, u))
+    return [FieldResults(distribution=[UniquesDistributionSimple(i, row[i]) for i in range(1, base + 1)],
+                         nice_numbers=nn) for row, nn in zip(rows, per)]
+
+
+def process_ranges_detailed_gpu(ctx: GpuContext, ranges, base: int) -> List[FieldResults]:
+    """process_range_detailed_gpu for every range of `ranges`, in one batched
+    call (GpuContext.detailed_ranges)."""
+    return _ranges_field_results(*ctx.detailed_ranges(ranges, base), base)
+
+
+def process_ranges_detailed_cpu(ranges, base: int, threads: int = 1) -> List[FieldResults]:
+    """process_range_detailed_cpu for every range of `ranges`."""
+    return _ranges_field_results(*detailed_ranges_cpu(ranges, base, threads=threads), base)
 
 
 def process_range_niceonly_cpu(range_: FieldSize, base: int,

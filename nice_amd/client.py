@@ -19,6 +19,7 @@ merged in chunk order (compile_results).  No GPU is touched in that mode.
 
     python -m nice_amd detailed --benchmark extra-large --gpu
     python -m nice_amd --benchmark base-ten            # CPU mode
+    python -m nice_amd --survey --base 50 --gpu        # distribution of a sampled base range
 """
 from __future__ import annotations
 
@@ -72,6 +73,12 @@ def parse_args(argv=None):
     p.add_argument("--sound", action="store_true", default=bool(env("NICE_SOUND")),
                    help="niceonly: the sound filter (no Filter C, which can drop numbers it has not "
                         "ruled out; a per-candidate prefix test instead) -- a complete answer")
+    p.add_argument("--survey", action="store_true",
+                   help="survey --base: the unique-digit distribution of a stratified sample of its "
+                        "valid range in one batched call (nice_amd/survey.py); with --gpu on the GPU")
+    p.add_argument("--windows", type=int, default=4096, help="--survey: sample windows (strata)")
+    p.add_argument("--window-size", type=int, default=100_000, help="--survey: numbers per window")
+    p.add_argument("--seed", type=int, default=0, help="--survey: seed of the window offsets")
     return p.parse_args(argv)
 
 
@@ -184,6 +191,23 @@ def run_once(args, ctx) -> int:
     return 0
 
 
+def run_survey(args, ctx) -> int:
+    """--survey: print the sampled distribution of --base as one JSON line."""
+    from .survey import survey_base
+    if not args.base:
+        log.error("--survey needs --base")
+        return 2
+    t0 = time.perf_counter()
+    r = survey_base(ctx, args.base, args.windows, args.window_size, args.seed, threads=max(1, args.threads))
+    elapsed = time.perf_counter() - t0
+    log.info("✓ Surveyed %.2e numbers of base %d in %.2fs", r.numbers, args.base, elapsed)
+    print(json.dumps({"base": r.base, "windows": len(r.windows), "window_size": args.window_size,
+                      "seed": args.seed, "numbers": r.numbers, "mean": r.mean, "stdev": r.stdev,
+                      "distribution": r.distribution,
+                      "near_misses": [[str(n), u] for n, u in r.near_misses]}))
+    return 0
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     level = {"off": logging.CRITICAL + 10, "error": logging.ERROR, "warn": logging.WARNING,
@@ -199,6 +223,8 @@ def main(argv=None) -> int:
             return 1
     else:
         log.info("CPU mode: %d threads", args.threads)
+    if args.survey:
+        return run_survey(args, ctx)
     while True:
         rc = run_once(args, ctx)
         if rc or not args.repeat:

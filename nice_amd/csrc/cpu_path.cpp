@@ -216,6 +216,52 @@ extern "C" int nice_cpu_process_range_detailed(uint64_t start_lo, uint64_t start
     return with_base(base, [&](const auto &bp) { return detailed_cpu(s, e, bp, threads, hist, out, cap, n_out); });
 }
 
+// The batched-ranges call on the host cores: the CPU path range by range.
+extern "C" int nice_cpu_process_ranges_detailed(uint32_t base, const uint64_t *bounds, size_t n_ranges,
+                                                uint32_t flags, int32_t threads, uint64_t *hist,
+                                                nice_number *out, uint32_t *out_range, size_t cap,
+                                                size_t *n_out) {
+    if (!bounds || !hist || !n_out || (cap && !out)) return cpu_fail(NICE_ERR_INVALID, "null argument");
+    if (base < 2 || base > 128) return cpu_fail(NICE_ERR_INVALID, "base must be in 2..128");
+    if (flags > NICE_RANGES_SUM) return cpu_fail(NICE_ERR_INVALID, "bad flags");
+    if (n_ranges == 0 || n_ranges > ((size_t)1 << 20))
+        return cpu_fail(NICE_ERR_INVALID, "n_ranges must be in 1..2^20");
+    for (size_t i = 0; i < n_ranges; i++)
+        if (mk(bounds[4 * i], bounds[4 * i + 1]) >= mk(bounds[4 * i + 2], bounds[4 * i + 3]))
+            return cpu_fail(NICE_ERR_INVALID, ("range " + std::to_string(i) + " is empty or inverted").c_str());
+    const bool sum = flags == NICE_RANGES_SUM;
+    const size_t nb = base + 1;
+    std::vector<uint64_t> row(nb);
+    std::vector<nice_number> list, one;
+    std::vector<uint32_t> idx;
+    if (sum) std::fill(hist, hist + nb, 0);
+    for (size_t i = 0; i < n_ranges; i++) {
+        const uint64_t *b = bounds + 4 * i;
+        size_t n = 0;
+        int rc = nice_cpu_process_range_detailed(b[0], b[1], b[2], b[3], base, threads, row.data(), one.data(),
+                                                 one.size(), &n);
+        if (rc == NICE_ERR_CAPACITY) {
+            one.resize(n);
+            rc = nice_cpu_process_range_detailed(b[0], b[1], b[2], b[3], base, threads, row.data(), one.data(),
+                                                 one.size(), &n);
+        }
+        if (rc) return rc;
+        for (size_t u = 0; u < nb; u++) {
+            if (sum) hist[u] += row[u];
+            else hist[i * nb + u] = row[u];
+        }
+        list.insert(list.end(), one.begin(), one.begin() + n);
+        idx.insert(idx.end(), n, (uint32_t)i);
+    }
+    *n_out = list.size();
+    if (list.size() > cap) return cpu_fail(NICE_ERR_CAPACITY, "output capacity too small (n_out = required)");
+    for (size_t j = 0; j < list.size(); j++) {
+        out[j] = list[j];
+        if (out_range) out_range[j] = idx[j];
+    }
+    return NICE_OK;
+}
+
 extern "C" int nice_cpu_process_range_niceonly_ex(uint64_t start_lo, uint64_t start_hi, uint64_t end_lo,
                                                   uint64_t end_hi, uint32_t base, uint32_t stride_k,
                                                   int32_t threads, uint32_t filter, nice_number *out,

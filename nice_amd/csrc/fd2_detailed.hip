@@ -172,6 +172,106 @@ hipError_t launch_detailed_fd2(const DetailedLaunch &p, int num_cus, hipStream_t
     return hipSuccess;
 }
 
+// ---------------------------------------------------------------------------
+// Batched ranges.
+// ---------------------------------------------------------------------------
+namespace fd2 {
+using BatchFn = hipError_t (*)(const BatchLaunch &, int, int, int, const void *, uint32_t, hipStream_t);
+hipError_t launch_batch_part0(const BatchLaunch &, int, int, int, const void *, uint32_t, hipStream_t);
+hipError_t launch_batch_part1(const BatchLaunch &, int, int, int, const void *, uint32_t, hipStream_t);
+hipError_t launch_batch_part2(const BatchLaunch &, int, int, int, const void *, uint32_t, hipStream_t);
+hipError_t launch_batch_part3(const BatchLaunch &, int, int, int, const void *, uint32_t, hipStream_t);
+hipError_t launch_batch_part4(const BatchLaunch &, int, int, int, const void *, uint32_t, hipStream_t);
+hipError_t launch_batch_part5(const BatchLaunch &, int, int, int, const void *, uint32_t, hipStream_t);
+static_assert(FD2_NPARTS == 6, "launch_batch_part declarations");
+}  // namespace fd2
+
+uint32_t fd2_batch_wg(uint32_t base) {
+    return (fd2::valu_limbs((int)base) & 1024) ? (uint32_t)fd2::big_wg((int)base) : 512u;
+}
+
+// The base's TCHUNK (Cfg), made odd as launch_cfg makes its chunks: odd chunks
+// spread a wave's low-digit entries over distinct bank pairs, and are never a
+// multiple of 16 (the bases without a low-digit table).
+uint32_t fd2_batch_chunk(uint32_t base) { return (base <= 45 ? 80u : (base <= 58 ? 160u : 240u)) + 1; }
+
+void fd2_batch_plan(uint32_t base, u128 a, u128 e, uint32_t row, std::vector<BatchUnit> &out) {
+    const fd2::BaseThresholds &t = fd2::thresholds(base);
+    const u64 wg = fd2_batch_wg(base), tchunk = fd2_batch_chunk(base);
+    for (size_t i = 0; i <= t.cuts.size() && a < e; i++) {
+        const u128 stop = i < t.cuts.size() && t.cuts[i] < e ? t.cuts[i] : e;
+        if (stop <= a) continue;
+        const u128 cnt = stop - a;
+        // Whole workgroups of chunks <= the base's target, as launch_cfg's
+        // whole rounds: the fewest workgroups that hold the piece, then the
+        // chunk that fills them (so the last main workgroup is nearly full).
+        // A piece of <= WG numbers is one workgroup of one number per lane (a
+        // lane's steps are the latency of a small range).
+        const u128 nwg = (cnt + (u128)wg * tchunk - 1) / ((u128)wg * tchunk);
+        u64 chunk = (u64)((cnt + nwg * wg - 1) / (nwg * wg));
+        if (chunk > 1 && chunk % 2 == 0) chunk++;  // <= tchunk, which is odd
+        u128 units = cnt / chunk;  // lanes of `chunk` numbers
+        const u64 tail = (u64)(cnt - units * chunk);
+        u128 n = a;
+        while (units) {
+            const u64 lanes = units < wg ? (u64)units : wg;
+            out.push_back(BatchUnit{(u64)n, (u64)(n >> 64), (uint32_t)lanes, (uint32_t)chunk, row, (uint32_t)i});
+            n += (u128)lanes * chunk;
+            units -= lanes;
+        }
+        if (tail) out.push_back(BatchUnit{(u64)n, (u64)(n >> 64), (uint32_t)tail, 1u, row, (uint32_t)i});
+        a = stop;
+    }
+}
+
+hipError_t launch_detailed_fd2_batch(const BatchLaunch &p, hipStream_t s) {
+    if (!fd2_supported(p.base) || !p.n_units || p.n_units > 0x7fffffffull) return hipErrorInvalidValue;
+    const fd2::BaseThresholds &t = fd2::thresholds(p.base);
+    const size_t nc = t.combos.size();
+    const u32 B = p.base * p.base;
+    const int dn = p.base % 5 == 0 ? p.base / 5 : p.base / 5 + 1, nx = (dn + 1) / 2;  // Cfg::DN, NX
+    // init_at reads the digits only where n passes 64 bits and the kernel
+    // keeps 32-bit init columns (Cfg::N64, C64)
+    const bool digits = !fd2::fits64(p.base, dn) && fd2_batch_wg(p.base) < 1024;
+    // descriptors grouped by combo (a counting sort: the order within a combo
+    // is the plan's, ascending n within a range)
+    std::vector<size_t> first(nc + 1, 0);
+    for (size_t i = 0; i < p.n_units; i++) {
+        if (p.units[i].combo >= nc) return hipErrorInvalidValue;
+        first[p.units[i].combo + 1]++;
+    }
+    for (size_t c = 0; c < nc; c++) first[c + 1] += first[c];
+    std::vector<size_t> at(first.begin(), first.end() - 1);
+    fd2::Fd2Unit *h = (fd2::Fd2Unit *)p.h_desc;
+    static_assert(sizeof(fd2::Fd2Unit) == kBatchDescBytes, "descriptor size");
+    for (size_t i = 0; i < p.n_units; i++) {
+        const BatchUnit &u = p.units[i];
+        fd2::Fd2Unit &d = h[at[u.combo]++];
+        d.lo = u.lo;
+        d.hi = u.hi;
+        d.lanes = u.lanes;
+        d.chunk = u.chunk;
+        d.row = u.row;
+        d.pad = 0;
+        for (int k = 0; k < fd2::kXDigits; k++) d.xs[k] = 0;
+        if (digits) fd2::host_digits(((u128)u.hi << 64) | u.lo, B, d.xs, nx);
+    }
+    hipError_t err = hipMemcpyAsync(p.d_desc, p.h_desc, p.n_units * kBatchDescBytes, hipMemcpyHostToDevice, s);
+    if (err != hipSuccess) return err;
+    static const fd2::BatchFn parts[FD2_NPARTS] = {fd2::launch_batch_part0, fd2::launch_batch_part1,
+                                                   fd2::launch_batch_part2, fd2::launch_batch_part3,
+                                                   fd2::launch_batch_part4, fd2::launch_batch_part5};
+    for (size_t c = 0; c < nc; c++) {
+        const size_t n = first[c + 1] - first[c];
+        if (!n) continue;
+        const fd2::Combo &cb = t.combos[c];
+        err = parts[fd2_part_of((int)p.base)](p, cb.nd, cb.ne, cb.ne2,
+                                              (const fd2::Fd2Unit *)p.d_desc + first[c], (uint32_t)n, s);
+        if (err != hipSuccess) return err == hipErrorNotFound ? hipErrorInvalidValue : err;
+    }
+    return hipSuccess;
+}
+
 }  // namespace nice
 
 #include NICE_PROBE_INC("fd2_detailed_probe_exports.inc")

@@ -1735,6 +1735,72 @@ __device__ __forceinline__ void walk_sib(State<P> (&st)[P::SIB], const unsigned 
     }
 }
 
+// fd2_batch_kernel's copies of fd2_body's first and last steps.  fd2_body keeps
+// its own text: with these two called from it instead, every fd2_kernel kept
+// its resource line but 6 369 instructions across the 131 instantiations came
+// out in another order (scripts/isa/kernel_diff.py), and the field kernels'
+// generated code is not to move for a feature they do not use.  Keep the two
+// in step with fd2_body.
+//
+// A workgroup's start: the table image DMA'd into LDS and the histogram
+// region zeroed (see fd2_body).
+template <class P>
+__device__ __forceinline__ void fd2_load_tables(unsigned char *smem, const uint4 *tabs, u32 tid) {
+    constexpr u32 N16 = (u32)(P::TAB_BYTES / 16);
+    const u32 lane = tid & 63, w64 = tid & ~63u;
+    for (u32 i0 = w64; i0 < N16; i0 += P::WG)
+        if (i0 + lane < N16)
+            __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void *)(tabs + i0 + lane),
+                                             (__attribute__((address_space(3))) void *)(smem + P::TC0 + 16 * i0),
+                                             16, 0, 0);
+    uint4 *h4 = (uint4 *)smem;
+    for (u32 i = tid; i < (u32)(P::ZA / 16); i += P::WG) h4[i] = make_uint4(0, 0, 0, 0);
+    if constexpr (P::SPLIT)
+        for (u32 i = tid; i < (u32)(P::HIST_BYTES / 16); i += P::WG)
+            h4[P::HB / 16 + i] = make_uint4(0, 0, 0, 0);
+}
+
+// A workgroup's end (after the barrier that follows its steps): the window
+// rows reduced and, with the out-of-window bins, added to row `row` (129 bins
+// apart) of hist_rows.
+template <class P>
+__device__ __forceinline__ void fd2_flush(const unsigned char *smem, u64 *hist_rows, u32 row_out, u32 tid) {
+    const u32 *hist = (const u32 *)(smem + P::HB);
+    const u32 *outl = (const u32 *)(smem + P::OUTL);
+    const u32 lane = tid & 63, wave = tid >> 6;
+    u64 *hist_out = hist_rows + row_out * 129;
+    // Window rows: wave w sums rows w, w + WG/64, ...; all of a wave's rows
+    // are read and reduced together, so their cross-lane steps overlap.
+    constexpr u32 NWAVE = P::WG / 64, RPW = (P::W + NWAVE - 1) / NWAVE;
+    u32 rs[RPW];
+#pragma unroll
+    for (u32 k = 0; k < RPW; k++) {
+        const u32 row = wave + k * NWAVE;
+        u32 s = 0;
+        if (row < (u32)P::W) {
+#pragma unroll
+            for (int q = 0; q < P::HROW / 64; q++) {
+                const u32 v = hist[row * P::HROW + lane + 64 * q];
+                if constexpr (P::HQ == 2) s += (v & 0xffffu) + (v >> 16);
+                else s += (v & 0xffu) + ((v >> 8) & 0xffu) + ((v >> 16) & 0xffu) + (v >> 24);
+            }
+        }
+        rs[k] = s;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+#pragma unroll
+        for (u32 k = 0; k < RPW; k++) rs[k] += __shfl_xor(rs[k], o);
+#pragma unroll
+    for (u32 k = 0; k < RPW; k++) {
+        const u32 row = wave + k * NWAVE;
+        if (lane == 0 && row < (u32)P::W && rs[k])
+            atomicAdd((unsigned long long *)&hist_out[P::W0 + row], (unsigned long long)rs[k]);
+    }
+    if (tid < (u32)P::NBINS && outl[tid])
+        atomicAdd((unsigned long long *)&hist_out[tid], (unsigned long long)outl[tid]);
+}
+
 // Persistent grid: batch b of the launch (64 lanes' units) -> this lane's
 // unit: b < mb: main unit 64 b + lane (chunk a.chunk from a.start); else the
 // tail numbers 64 (b - mb) + lane (chunk 1 from a.tail).
@@ -1957,6 +2023,92 @@ template <class P>
 __global__ void __launch_bounds__(P::WG) __attribute__((amdgpu_waves_per_eu(P::WPE, P::WPE)))
 fd2_kernel(Fd2Args a) {
     fd2_body<P>(a);
+}
+
+// ---------------------------------------------------------------------------
+// Batched ranges: one grid whose workgroups belong to different ranges.
+// Workgroup blockIdx.x reads ONE descriptor (wave-uniform: scalar loads, every
+// walk parameter stays in SGPRs as in fd2_body) and runs the same device code
+// -- table DMA, init / init_at, walk_chunk, the window-row reduction and the
+// out-of-window bins -- over lanes x chunk numbers from its first n, then
+// flushes into its range's own histogram row (or, sum mode, into copy
+// blockIdx.x % ncopies as single fields do).  Near-misses go to the launch's
+// shared NumOut.  No in-kernel finish (a batch has no single result row to
+// publish; the host reads the rows back), no sibling lanes, no persistent grid:
+// rounds of workgroups, the configuration small fields run.
+// ---------------------------------------------------------------------------
+constexpr int kXDigits = 12;  // Fd2Args::xs / Fd2Unit::xs (>= NX of every FD base)
+struct Fd2Unit {
+    u64 lo, hi;   // first n
+    u32 lanes;    // active lanes (<= WG)
+    u32 chunk;    // numbers per lane (<= B); 1 for a tail workgroup
+    u32 row;      // result row (per-range mode)
+    u32 pad;
+    u32 xs[kXDigits];  // radix-B digits of the first n (init_at; bases whose n passes 64 bits)
+};
+static_assert(sizeof(Fd2Unit) == 80, "descriptor layout");
+
+struct Fd2BatchArgs {
+    const Fd2Unit *units;  // one per workgroup
+    u64 *hist;             // rows of 129 bins
+    u32 ncopies;           // 0: row = the descriptor's; else blockIdx.x % ncopies (sum mode)
+    u32 cutoff;
+    NumOut out;
+    const uint4 *tabs;
+};
+
+// The batch kernel's configuration for a (base, combo): what try_combo picks
+// for a small field, with rounds of workgroups.  LG_ and PERS_ are spelled out
+// at the values those kernels default to (two mask words or 512 threads: no
+// lookup groups), which makes the type -- and with it every device function
+// instantiated for it -- the batch kernel's own: sharing the instantiations
+// with fd2_kernel<P> of the same P moved that kernel's register allocation
+// by a VGPR or two (profiles/ranges/build_and_resources.txt).
+template <int B_, int ND_, int NE_, int NE2_>
+using BatchCfg = std::conditional_t<(valu_limbs(B_) & 1024) == 0,
+                                    Cfg<B_, ND_, NE_, NE2_, 0, 512, valu_limbs(B_), 0, 0>,
+                                    Cfg<B_, ND_, NE_, NE2_, 0, big_wg(B_), valu_limbs_big(B_, ND_, NE_), 0, 0>>;
+
+template <class P>
+__global__ void __launch_bounds__(P::WG) __attribute__((amdgpu_waves_per_eu(P::WPE, P::WPE)))
+fd2_batch_kernel(Fd2BatchArgs a) {
+    static_assert(!P::PERS && P::SIB == 1 && P::PROBE == 0, "batch kernel: rounds, regular lanes");
+    static_assert(!(P::MW == 3 && P::WG >= 1024) && P::LGW == 0, "BatchCfg spells out the default lookup groups");
+    __shared__ __attribute__((aligned(16))) unsigned char smem[P::LDS_BYTES];
+    u32 *outl = (u32 *)(smem + P::OUTL);
+    const u32 tid = threadIdx.x;
+    // The descriptor, indexed by blockIdx.x only: read before anything is
+    // written, so the loads are scalar.
+    const Fd2Unit *__restrict__ d = a.units + blockIdx.x;
+    const u64 start_lo = d->lo, start_hi = d->hi;
+    const u32 lanes = d->lanes, chunk = d->chunk;
+    const u32 row = a.ncopies ? blockIdx.x % a.ncopies : d->row;
+    u32 xs[P::NX];
+    if constexpr (!P::N64 && !P::C64) {
+#pragma unroll
+        for (int i = 0; i < P::NX; i++) xs[i] = d->xs[i];
+    }
+    const NumOut out = a.out;
+    const u32 cutoff = a.cutoff;
+    fd2_load_tables<P>(smem, a.tabs, tid);
+    const bool active = tid < lanes;
+    const u64 n0_off = (u64)tid * chunk;
+    u64 n0_lo = start_lo, n0_hi = start_hi;
+    add_u128(n0_lo, n0_hi, n0_off);
+    const u32 hbase = P::HB + tid % P::HROW * 4;
+    const u32 hinc = __builtin_amdgcn_readfirstlane(1u << (32 / P::HQ * (tid / P::HROW)));
+    u32 probe_acc = 0;
+    State<P> st;
+    if constexpr (P::N64 || P::C64) {
+        if (active) init<P>(st, n0_lo, n0_hi);
+    } else {
+        if (active) init_at<P>(st, xs, n0_off, n0_lo, n0_hi);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (active) walk_chunk<P>(st, smem, chunk, n0_lo, n0_hi, hbase, hinc, outl, cutoff, out, probe_acc);
+    __syncthreads();
+    fd2_flush<P>(smem, a.hist, row, tid);  // row < 2^14 rows of a pass: row * 129 fits 32 bits
 }
 
 template <class P>
@@ -2268,6 +2420,26 @@ static hipError_t launch_cfg(const DetailedLaunch &p, int num_cus, hipStream_t s
     return hipSuccess;
 }
 
+
+// One batch launch: `n` descriptors (all of this P's combo) from `units`.
+template <class P>
+static hipError_t launch_batch_cfg(const BatchLaunch &p, const Fd2Unit *units, u32 n, hipStream_t s) {
+    if (p.cutoff + 1 < (u32)(P::W0 + P::W)) return hipErrorInvalidValue;
+    const uint4 *tabs = nullptr;
+    hipError_t e = fd2_tables<P>(s, &tabs);
+    if (e != hipSuccess) return e;
+    Fd2BatchArgs a{};
+    a.units = units;
+    a.hist = p.hist;
+    a.ncopies = p.ncopies;
+    a.cutoff = p.cutoff;
+    a.out = p.out;
+    a.tabs = tabs;
+    hipLaunchKernelGGL(fd2_batch_kernel<P>, dim3(n), dim3(P::WG), 0, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (p.launches) ++*p.launches;
+    return hipSuccess;
+}
 
 // Sibling-lane launches (Cfg::SIB = M > 1).  A segment [a, a + count) is
 // Q super-blocks of M B^2 numbers plus a remainder R < M B^2.  Super-block q

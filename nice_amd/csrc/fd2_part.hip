@@ -76,5 +76,18 @@ hipError_t FD2_CAT(launch_part, FD2_PART)(const DetailedLaunch &p, int nd, int n
     return hipErrorNotFound;
 }
 
+// The batch kernel (fd2_batch_kernel) of a (base, combo): n descriptors.
+hipError_t FD2_CAT(launch_batch_part, FD2_PART)(const BatchLaunch &p, int nd, int ne, int ne2,
+                                                const void *units, uint32_t n, hipStream_t s) {
+#define X(B_, ND_, NE_, NE2_)                                                                   \
+    if constexpr (fd2_part_of(B_) == FD2_PART) {                                                \
+        if ((int)p.base == B_ && nd == ND_ && ne == NE_ && ne2 == NE2_)                         \
+            return launch_batch_cfg<BatchCfg<B_, ND_, NE_, NE2_>>(p, (const Fd2Unit *)units, n, s); \
+    }
+    FD2_COMBOS(X)
+#undef X
+    return hipErrorNotFound;
+}
+
 }  // namespace fd2
 }  // namespace nice

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace nice {
 
 // Near-miss / nice-number output buffer on the device.
@@ -60,6 +62,39 @@ bool fd2_supported(uint32_t base);
 hipError_t launch_detailed_fd2(const DetailedLaunch &p, int num_cus, hipStream_t s);
 // The n where fd2's per-segment limb layout changes (ascending).
 size_t fd2_cuts(uint32_t base, unsigned __int128 *out, size_t cap);
+// Batched ranges (fd2_batch_kernel, fd2_kernel.hpp): many small in-range
+// ranges in one launch per limb layout.  A unit is one workgroup: `lanes`
+// lanes walk `chunk` numbers each from n = (lo, hi), and flush into histogram
+// row `row`; `combo` indexes the base's cut intervals (fd2_cuts).
+struct BatchUnit {
+    uint64_t lo, hi;
+    uint32_t lanes, chunk;
+    uint32_t row, combo;
+};
+constexpr size_t kBatchDescBytes = 80;  // device descriptor per unit (Fd2Unit)
+// Workgroup size and target chunk of a base's batch kernel.
+uint32_t fd2_batch_wg(uint32_t base);
+uint32_t fd2_batch_chunk(uint32_t base);
+// The units of [start, end) (inside the base's valid range): cut at the limb
+// layout changes, each piece tiled into main workgroups (one chunk per lane)
+// plus at most one tail workgroup (the < chunk numbers left over, one per
+// lane).  Appended to `out` in ascending n.  Pure host code.
+void fd2_batch_plan(uint32_t base, unsigned __int128 start, unsigned __int128 end, uint32_t row,
+                    std::vector<BatchUnit> &out);
+struct BatchLaunch {
+    uint32_t base;
+    uint32_t cutoff;
+    const BatchUnit *units;  // host
+    size_t n_units;
+    void *h_desc, *d_desc;   // pinned staging / device array, n_units x kBatchDescBytes
+    uint64_t *hist;          // rows of 129 u64 bins (zeroed by the caller)
+    uint32_t ncopies;        // 0: unit.row selects the row; else workgroup b flushes into row b % ncopies
+    NumOut out;
+    uint32_t *launches;      // if set, incremented per kernel launch enqueued
+};
+// Groups the units by combo, copies their descriptors (async, on s) and
+// enqueues one launch per combo present.
+hipError_t launch_detailed_fd2_batch(const BatchLaunch &p, hipStream_t s);
 // Test hook: every later sibling-lane launch of the process uses lane stride
 // L (odd; 0 restores the production pick, fd2_kernel.hpp launch_sib).
 void fd2_force_sib_stride(uint32_t L);
