@@ -292,6 +292,26 @@ uint32_t nice_host_threads(void);
  * model's pick, and fields of >= 4 super-blocks take the sibling kernel
  * whatever their size; 0 restores production.  NICE_ERR_INVALID otherwise. */
 int nice_debug_force_sib_stride(uint32_t L);
+/* Test hook: the compile-time histogram window [w0, w0 + w) of the FD kernel
+ * of `base`: unique counts inside it are counted in LDS, the others take the
+ * kernel's out-of-window branch, which also lists the near-misses.
+ * NICE_ERR_INVALID for a base without an FD kernel.  No device needed. */
+int nice_debug_fd_window(uint32_t base, uint32_t *w0, uint32_t *w);
+/* Test hook: every later GPU detailed call of this process at `base`
+ * (nice_process_range_detailed, nice_detailed_submit / _collect,
+ * nice_process_ranges_detailed and its per-range fallbacks) lists the numbers
+ * with num_uniques > cutoff instead of > nice_near_miss_cutoff(base) -- the
+ * FD and the generic launches of a field alike, and the self-check of the
+ * result runs against the same cutoff.  The histograms do not change.  With
+ * cutoff = w0 + w - 1 every number on the high out-of-window branch is listed,
+ * so a test sees the list code that production takes about once in 1e8
+ * numbers.  0 restores production for that base.  NICE_ERR_INVALID when the
+ * base has no FD kernel or cutoff is neither 0 nor in [w0 + w - 1, base - 1].
+ * Set it with no field of that base in flight (a field submitted under one
+ * cutoff and collected under another fails its self-check).  The CPU API,
+ * niceonly and nice_validate_detailed keep the production cutoff.  No device
+ * needed to set it. */
+int nice_debug_set_near_miss_cutoff(uint32_t base, uint32_t cutoff);
 /* Test hook: the cpu.max cap nice_host_threads applies for the cgroup
  * `cgroup_path` under a cgroup2 mount at `root` (0 = no quota). */
 uint32_t nice_debug_cgroup_cpus(const char *root, const char *cgroup_path);

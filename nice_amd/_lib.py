@@ -49,7 +49,7 @@ EXPORTS = (
     "nice_niceonly_prefix_rejected", "nice_msd_valid_ranges_ex", "nice_cpu_process_range_niceonly_ex",
     "nice_check_prefix_reject_inrange",
     "nice_process_ranges_detailed", "nice_last_ranges_stats", "nice_cpu_process_ranges_detailed",
-    "nice_debug_ranges_plan",
+    "nice_debug_ranges_plan", "nice_debug_set_near_miss_cutoff", "nice_debug_fd_window",
 )
 
 
@@ -167,6 +167,8 @@ def lib():
         "nice_host_threads": ([], u32),
         "nice_debug_cgroup_cpus": ([ctypes.c_char_p, ctypes.c_char_p], u32),
         "nice_debug_force_sib_stride": ([u32], i32),
+        "nice_debug_set_near_miss_cutoff": ([u32, u32], i32),
+        "nice_debug_fd_window": ([u32, P32, P32], i32),
         "nice_process_ranges_detailed": ([vp, u32, P64, sz, u32, P64, PN, P32, sz, PSZ], i32),
         "nice_last_ranges_stats": ([vp, ctypes.POINTER(nice_ranges_stats)], i32),
         "nice_cpu_process_ranges_detailed": ([u32, P64, sz, u32, i32, P64, PN, P32, sz, PSZ], i32),

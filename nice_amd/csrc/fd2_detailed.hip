@@ -140,6 +140,15 @@ bool fd2_supported(uint32_t base) {
     }
 }
 
+bool fd2_window(uint32_t base, uint32_t *w0, uint32_t *w) {
+    switch (base) {
+#define X(b) case b: *w0 = fd2::window_w0(b), *w = fd2::window_w(b); return true;
+        FD2_BASES(X)
+#undef X
+    default: return false;
+    }
+}
+
 size_t fd2_cuts(uint32_t base, unsigned __int128 *out, size_t cap) {
     if (!fd2_supported(base)) return 0;
     const fd2::BaseThresholds &t = fd2::thresholds(base);

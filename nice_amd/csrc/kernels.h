@@ -98,6 +98,10 @@ hipError_t launch_detailed_fd2_batch(const BatchLaunch &p, hipStream_t s);
 // Test hook: every later sibling-lane launch of the process uses lane stride
 // L (odd; 0 restores the production pick, fd2_kernel.hpp launch_sib).
 void fd2_force_sib_stride(uint32_t L);
+// The base's compile-time histogram window [w0, w0 + w) (fd2_kernel.hpp
+// window_w0 / window_w); false for a base without an FD kernel.  The FD
+// launchers accept a cutoff with cutoff + 1 >= w0 + w.
+bool fd2_window(uint32_t base, uint32_t *w0, uint32_t *w);
 // Field epilogue on the launch stream: out_mapped[0..128] = the summed
 // histogram copies, out_mapped[129] = *count; copies and counter are zeroed.
 hipError_t launch_detailed_finish(uint64_t *hist, uint32_t *count, uint64_t *out_mapped, hipStream_t s);

@@ -518,19 +518,28 @@ int emit_list(std::vector<Entry> &all, nice_number *out, size_t cap, size_t *n_o
     return NICE_OK;
 }
 
+// nice_debug_set_near_miss_cutoff: per base, the cutoff the GPU detailed paths
+// use instead of near_miss_cutoff(base) (0: production).
+std::atomic<uint32_t> g_cutoff_override[129];
+
+uint32_t effective_cutoff(uint32_t base) {
+    const uint32_t c = base <= 128 ? g_cutoff_override[base].load(std::memory_order_relaxed) : 0u;
+    return c ? c : nice::near_miss_cutoff(base);
+}
+
 // The server's submit invariants for a detailed result (api/src/main.rs:
 // 309-359): the distribution sums to the field size; for every bin above the
 // near-miss cutoff the count equals the number of listed numbers with that
 // unique count; the list holds exactly the numbers above the cutoff.  (The
 // server's last check, recomputing each listed number, runs on the device in
-// nice_process_range_detailed.)  get(i) -> {n, u} of list entry i.
+// nice_process_range_detailed.)  get(i) -> {n, u} of list entry i.  cutoff:
+// the one the result was computed with (effective_cutoff for a GPU result).
 template <class Get>
-int validate_detailed(uint32_t base, u128 size, const uint64_t *hist, size_t n, Get get) {
+int validate_detailed(uint32_t base, uint32_t cutoff, u128 size, const uint64_t *hist, size_t n, Get get) {
     u128 sum = 0;
     for (uint32_t b = 0; b <= base; b++) sum += hist[b];
     if (sum != size)
         return fail(NICE_ERR_HIP, "self-check: distribution total does not equal the field size");
-    const uint32_t cutoff = nice::near_miss_cutoff(base);
     std::vector<uint64_t> per(base + 1, 0);
     for (size_t i = 0; i < n; i++) {
         const uint32_t u = get(i).u;
@@ -561,7 +570,7 @@ int validate_detailed(uint32_t base, u128 size, const uint64_t *hist, size_t n, 
 int enqueue_detailed(Device &d, Slot &sl, u128 s, u128 e, uint32_t base, bool *finished) {
     nice::DetailedLaunch p{};
     p.base = base;
-    p.cutoff = nice::near_miss_cutoff(base);
+    p.cutoff = effective_cutoff(base);
     p.hist = sl.d_state;
     p.out = nice::NumOut{sl.det.n, sl.det.u, sl.d_count, sl.det.cap};
     p.launches = &sl.launches;
@@ -855,7 +864,7 @@ int detailed_gather(nice_ctx *ctx, DetJob &job, int t) {
     off[nd] = job.all.size();
     // Self-check: the server's submit invariants (api/src/main.rs:309-359)
     // before anything is returned.
-    int rc = validate_detailed(base, job.e - job.s, job.total.data(), job.all.size(),
+    int rc = validate_detailed(base, effective_cutoff(base), job.e - job.s, job.total.data(), job.all.size(),
                                [&](size_t i) { return job.all[i]; });
     if (rc) return rc;
     if (!job.all.empty()) {
@@ -1170,7 +1179,8 @@ extern "C" {
 int nice_validate_detailed(uint32_t base, uint64_t size_lo, uint64_t size_hi, const uint64_t *hist,
                            const nice_number *list, size_t n) {
     if (base < 2 || base > 128 || !hist || (n && !list)) return fail(NICE_ERR_INVALID, "bad args");
-    const int rc = validate_detailed(base, mk(size_lo, size_hi), hist, n, [&](size_t i) {
+    // the server's cutoff, whatever nice_debug_set_near_miss_cutoff has set
+    const int rc = validate_detailed(base, nice::near_miss_cutoff(base), mk(size_lo, size_hi), hist, n, [&](size_t i) {
         return Entry{mk(list[i].number_lo, list[i].number_hi), list[i].num_uniques};
     });
     return rc ? NICE_ERR_INVALID : NICE_OK;
@@ -1483,6 +1493,24 @@ int nice_debug_force_sib_stride(uint32_t L) {
     if (L && (L % 2 == 0 || L > 255))
         return fail(NICE_ERR_INVALID, "sibling lane stride must be odd and <= 255 (0: the production pick)");
     nice::fd2_force_sib_stride(L);
+    return NICE_OK;
+}
+
+int nice_debug_fd_window(uint32_t base, uint32_t *w0, uint32_t *w) {
+    if (!w0 || !w) return fail(NICE_ERR_INVALID, "null argument");
+    if (!nice::fd2_window(base, w0, w)) return fail(NICE_ERR_INVALID, "base has no FD kernel");
+    return NICE_OK;
+}
+
+int nice_debug_set_near_miss_cutoff(uint32_t base, uint32_t cutoff) {
+    uint32_t w0 = 0, w = 0;
+    if (!nice::fd2_window(base, &w0, &w)) return fail(NICE_ERR_INVALID, "base has no FD kernel");
+    // the FD launchers take any cutoff at or above the top of the histogram
+    // window; at cutoff >= base nothing would be listed
+    if (cutoff && (cutoff + 1 < w0 + w || cutoff >= base))
+        return fail(NICE_ERR_INVALID, "cutoff must be 0 (production) or in [" + std::to_string(w0 + w - 1) + ", " +
+                                          std::to_string(base - 1) + "]");
+    g_cutoff_override[base].store(cutoff, std::memory_order_relaxed);
     return NICE_OK;
 }
 
@@ -2232,7 +2260,7 @@ int ranges_enqueue(Device &d, RangesDev &r, const Pass &p, uint32_t base, bool s
     HIPCHK(hipMemsetAsync(r.d_count, 0, 4, r.stream));
     nice::BatchLaunch b{};
     b.base = base;
-    b.cutoff = nice::near_miss_cutoff(base);
+    b.cutoff = effective_cutoff(base);
     b.units = p.units.data();
     b.n_units = nu;
     b.h_desc = r.h_desc;
@@ -2534,7 +2562,7 @@ int nice_process_ranges_detailed(nice_ctx *ctx, uint32_t base, const uint64_t *b
         if (!sum) {
             u128 s, e;
             R(i, s, e);
-            int rc = validate_detailed(base, e - s, &st.hist[i * nb], per[i].size(),
+            int rc = validate_detailed(base, effective_cutoff(base), e - s, &st.hist[i * nb], per[i].size(),
                                        [&](size_t j) { return per[i][j]; });
             if (rc) return fail(rc, "range " + std::to_string(i) + ": " + g_err);
         }
@@ -2542,7 +2570,8 @@ int nice_process_ranges_detailed(nice_ctx *ctx, uint32_t base, const uint64_t *b
         st.list_range.insert(st.list_range.end(), per[i].size(), (uint32_t)i);
     }
     if (sum) {
-        int rc = validate_detailed(base, total, st.hist.data(), st.list.size(), [&](size_t j) { return st.list[j]; });
+        int rc = validate_detailed(base, effective_cutoff(base), total, st.hist.data(), st.list.size(),
+                                   [&](size_t j) { return st.list[j]; });
         if (rc) return rc;
     }
     return ranges_emit(st, hist, out, out_range, cap, n_out);

@@ -331,8 +331,9 @@ static void ml_push(misslist *m, u128 n, u32 u) {
         if (u > cutoff) ml_push(ml, n, u);                    \
     }
 
-static void detailed_range(u128 s, u128 e, u32 base, u64 *hist, misslist *ml) {
-    u32 cutoff = oracle_near_miss_cutoff(base);
+/* cutoff: numbers with more unique digits are listed (the reference's is
+ * oracle_near_miss_cutoff(base); the *_cutoff entry points take another). */
+static void detailed_range(u128 s, u128 e, u32 base, u32 cutoff, u64 *hist, misslist *ml) {
     switch (base) {
     case 10: DETAILED_LOOP(nud_10(n)); break;
     case 40: DETAILED_LOOP(nud_40(n)); break;
@@ -353,15 +354,23 @@ static int emit_misses(const misslist *ml, u64 *miss_n, u32 *miss_u, size_t cap,
     return ml->len > cap ? 1 : 0;
 }
 
-int oracle_process_range_detailed(u64 slo, u64 shi, u64 elo, u64 ehi, u32 base,
-                                  u64 *hist, u64 *miss_n, u32 *miss_u, size_t cap,
-                                  size_t *n_miss) {
+int oracle_process_range_detailed_cutoff(u64 slo, u64 shi, u64 elo, u64 ehi, u32 base,
+                                         u32 cutoff, u64 *hist, u64 *miss_n, u32 *miss_u,
+                                         size_t cap, size_t *n_miss) {
     memset(hist, 0, (base + 1) * sizeof(u64));
     misslist ml = {0};
-    detailed_range(mk(slo, shi), mk(elo, ehi), base, hist, &ml);
+    detailed_range(mk(slo, shi), mk(elo, ehi), base, cutoff, hist, &ml);
     int rc = emit_misses(&ml, miss_n, miss_u, cap, n_miss);
     free(ml.n); free(ml.u);
     return rc;
+}
+
+int oracle_process_range_detailed(u64 slo, u64 shi, u64 elo, u64 ehi, u32 base,
+                                  u64 *hist, u64 *miss_n, u32 *miss_u, size_t cap,
+                                  size_t *n_miss) {
+    return oracle_process_range_detailed_cutoff(slo, shi, elo, ehi, base,
+                                                oracle_near_miss_cutoff(base), hist, miss_n,
+                                                miss_u, cap, n_miss);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -380,6 +389,7 @@ typedef struct {
     u128 start, end, chunk;
     u64 nchunks;
     u32 base;
+    u32 cutoff; /* detailed: the near-miss cutoff */
     int mode; /* 0 detailed, 1 niceonly */
     uint64_t floor_size;
     atomic_ullong next;
@@ -405,7 +415,7 @@ static void *worker(void *arg) {
         u128 s = j->start + (u128)i * j->chunk;
         u128 e = s + j->chunk < j->end ? s + j->chunk : j->end;
         if (j->mode == 0) {
-            detailed_range(s, e, j->base, j->hists[i], &j->lists[i]);
+            detailed_range(s, e, j->base, j->cutoff, j->hists[i], &j->lists[i]);
         } else {
             j->cand_counts[i] = niceonly_range_impl(s, e, j->base, j->stride_res,
                                                     j->stride_count, j->stride_mod,
@@ -425,13 +435,18 @@ static void run_job(job *j, int threads) {
     for (int t = 0; t < threads; t++) pthread_join(th[t], NULL);
 }
 
-int oracle_process_field_detailed_mt(u64 slo, u64 shi, u64 elo, u64 ehi, u32 base,
-                                     int threads, u64 *hist, u64 *miss_n, u32 *miss_u,
-                                     size_t cap, size_t *n_miss) {
+/* chunk 0: the reference client's chunk size.  Any other chunking gives the
+ * same result (the lists are concatenated in chunk order); a test passes a
+ * small one to spread a short window over its threads. */
+int oracle_process_field_detailed_mt_cutoff(u64 slo, u64 shi, u64 elo, u64 ehi, u32 base,
+                                            int threads, u32 cutoff, u64 chunk, u64 *hist,
+                                            u64 *miss_n, u32 *miss_u, size_t cap,
+                                            size_t *n_miss) {
     job j;
     memset(&j, 0, sizeof(j));
     j.start = mk(slo, shi); j.end = mk(elo, ehi); j.base = base; j.mode = 0;
-    j.chunk = client_chunk_size(j.end - j.start);
+    j.cutoff = cutoff;
+    j.chunk = chunk ? chunk : client_chunk_size(j.end - j.start);
     j.nchunks = (u64)((j.end - j.start + j.chunk - 1) / j.chunk);
     atomic_init(&j.next, 0);
     j.hists = calloc(j.nchunks, sizeof(u64 *));
@@ -451,6 +466,14 @@ int oracle_process_field_detailed_mt(u64 slo, u64 shi, u64 elo, u64 ehi, u32 bas
     int rc = emit_misses(&all, miss_n, miss_u, cap, n_miss);
     free(all.n); free(all.u);
     return rc;
+}
+
+int oracle_process_field_detailed_mt(u64 slo, u64 shi, u64 elo, u64 ehi, u32 base,
+                                     int threads, u64 *hist, u64 *miss_n, u32 *miss_u,
+                                     size_t cap, size_t *n_miss) {
+    return oracle_process_field_detailed_mt_cutoff(slo, shi, elo, ehi, base, threads,
+                                                   oracle_near_miss_cutoff(base), 0, hist,
+                                                   miss_n, miss_u, cap, n_miss);
 }
 
 /* ------------------------------------------------------------------------ */

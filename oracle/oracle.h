@@ -59,6 +59,14 @@ int oracle_process_range_detailed(uint64_t start_lo, uint64_t start_hi,
                                   uint64_t *hist, uint64_t *miss_n, uint32_t *miss_u,
                                   size_t cap, size_t *n_miss);
 
+/* The same with an explicit cutoff: numbers with num_uniques > cutoff are
+ * listed, the histogram does not depend on it.  (A test hook lowers the GPU
+ * kernels' cutoff so their rare list branch is taken; this is its checker.) */
+int oracle_process_range_detailed_cutoff(uint64_t start_lo, uint64_t start_hi,
+                                         uint64_t end_lo, uint64_t end_hi, uint32_t base,
+                                         uint32_t cutoff, uint64_t *hist, uint64_t *miss_n,
+                                         uint32_t *miss_u, size_t cap, size_t *n_miss);
+
 /* client/src/main.rs:120-254 for SearchMode::Detailed: chunk the field as the
  * reference client does (1e6 * clamp(ceil(size/1e11), 1, 1000)), process the
  * chunks on `threads` POSIX threads, merge the histograms and concatenate the
@@ -67,6 +75,13 @@ int oracle_process_field_detailed_mt(uint64_t start_lo, uint64_t start_hi,
                                      uint64_t end_lo, uint64_t end_hi, uint32_t base,
                                      int threads, uint64_t *hist, uint64_t *miss_n,
                                      uint32_t *miss_u, size_t cap, size_t *n_miss);
+/* The same with an explicit cutoff and chunk size (0: the client's rule; the
+ * result does not depend on it). */
+int oracle_process_field_detailed_mt_cutoff(uint64_t start_lo, uint64_t start_hi,
+                                            uint64_t end_lo, uint64_t end_hi, uint32_t base,
+                                            int threads, uint32_t cutoff, uint64_t chunk,
+                                            uint64_t *hist, uint64_t *miss_n, uint32_t *miss_u,
+                                            size_t cap, size_t *n_miss);
 
 /* common/src/residue_filter.rs:6-11.  Writes the valid residues mod (b-1)
  * ascending into out (capacity base), returns their count. */

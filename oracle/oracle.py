@@ -52,6 +52,13 @@ def lib():
         L.oracle_process_field_detailed_mt.argtypes = [u64, u64, u64, u64, u32, i32, P64, P64,
                                                        P32, sz, ctypes.POINTER(sz)]
         L.oracle_process_field_detailed_mt.restype = i32
+        L.oracle_process_range_detailed_cutoff.argtypes = [u64, u64, u64, u64, u32, u32, P64, P64,
+                                                           P32, sz, ctypes.POINTER(sz)]
+        L.oracle_process_range_detailed_cutoff.restype = i32
+        L.oracle_process_field_detailed_mt_cutoff.argtypes = [u64, u64, u64, u64, u32, i32, u32,
+                                                              u64, P64, P64, P32, sz,
+                                                              ctypes.POINTER(sz)]
+        L.oracle_process_field_detailed_mt_cutoff.restype = i32
         L.oracle_residue_filter.argtypes = [u32, P32]
         L.oracle_residue_filter.restype = u32
         L.oracle_lsd_bitmap.argtypes = [u32, u32, P8]
@@ -133,15 +140,26 @@ def _detailed(fn, start, end, base, *extra, cap=None):
     return FieldResults(dist, nice)
 
 
-def process_range_detailed(start: int, end: int, base: int, cap=None) -> FieldResults:
-    """client_process.rs:150-191 on [start, end)."""
-    return _detailed(lib().oracle_process_range_detailed, start, end, base, cap=cap)
+def process_range_detailed(start: int, end: int, base: int, cap=None, cutoff=None) -> FieldResults:
+    """client_process.rs:150-191 on [start, end).  cutoff: list the numbers
+    with more unique digits than this instead of near_miss_cutoff(base)."""
+    if cutoff is None:
+        return _detailed(lib().oracle_process_range_detailed, start, end, base, cap=cap)
+    return _detailed(lib().oracle_process_range_detailed_cutoff, start, end, base, cutoff, cap=cap)
 
 
 def process_field_detailed_mt(start: int, end: int, base: int, threads: int,
-                              cap=None) -> FieldResults:
-    """client/src/main.rs:120-254 (detailed) on `threads` threads."""
-    return _detailed(lib().oracle_process_field_detailed_mt, start, end, base, threads, cap=cap)
+                              cap=None, cutoff=None, chunk: int = 0) -> FieldResults:
+    """client/src/main.rs:120-254 (detailed) on `threads` threads.  cutoff as
+    in process_range_detailed; chunk: the work unit of the threads (0 = the
+    client's rule, 1e6 for fields up to 1e11), which the result does not
+    depend on."""
+    if cutoff is None and not chunk:
+        return _detailed(lib().oracle_process_field_detailed_mt, start, end, base, threads, cap=cap)
+    if cutoff is None:
+        cutoff = near_miss_cutoff(base)
+    return _detailed(lib().oracle_process_field_detailed_mt_cutoff, start, end, base, threads,
+                     cutoff, chunk, cap=cap)
 
 
 def residue_filter(base: int) -> list:
