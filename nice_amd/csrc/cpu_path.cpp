@@ -195,7 +195,7 @@ int with_base(uint32_t base, F &&f) {
 }  // namespace
 
 namespace nice {
-void set_last_error(const char *msg);  // nice_abi.cpp: nice_last_error()'s thread-local message
+void set_last_error(const char *msg);  // abi_context.cpp: nice_last_error()'s thread-local message
 }
 
 namespace {

@@ -24,9 +24,9 @@ namespace nice {
 __global__ void __launch_bounds__(256)
 detailed_generic_kernel(u64 start_lo, u64 start_hi, u64 count, GenericBase g, u32 cutoff,
                         u64 *__restrict__ hist_out, NumOut out) {
-    __shared__ u32 hist[4][129];
+    __shared__ u32 hist[4][kHistBins];
     const u32 tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (u32 i = tid; i < 4 * 129; i += 256) (&hist[0][0])[i] = 0;
+    for (u32 i = tid; i < 4 * kHistBins; i += 256) (&hist[0][0])[i] = 0;
     __syncthreads();
     for (u64 idx = (u64)blockIdx.x * 256 + tid; idx < count; idx += (u64)gridDim.x * 256) {
         u64 lo = start_lo, hi = start_hi;
@@ -43,7 +43,7 @@ detailed_generic_kernel(u64 start_lo, u64 start_hi, u64 count, GenericBase g, u3
         }
     }
     __syncthreads();
-    hist_out += (blockIdx.x % kHistCopies) * 129;
+    hist_out += (blockIdx.x % kHistCopies) * kHistBins;
     for (u32 b = tid; b <= g.base; b += 256) {
         u32 s = hist[0][b] + hist[1][b] + hist[2][b] + hist[3][b];
         if (s) atomicAdd((unsigned long long *)&hist_out[b], (unsigned long long)s);
@@ -57,28 +57,28 @@ __global__ void unique_counts_kernel(const u64 *n_pairs, u32 count, GenericBase 
     if (i < count) out[i] = unique_generic(n_pairs[2 * i], n_pairs[2 * i + 1], g);
 }
 
-// Field epilogue: sum the kHistCopies histogram copies into `out` (129 bins,
-// then the near-miss count at out[129]) and zero the copies and the counter
+// Field epilogue: sum the kHistCopies histogram copies into `out` (kHistBins
+// bins, then the near-miss count at kFinCount) and zero the copies and the counter
 // for the next field.  `out` is mapped pinned host memory, so the host reads
 // the result straight after its completion event: no memset and no DMA copy
 // on the field's critical path.
 __global__ void __launch_bounds__(1024) detailed_finish_kernel(u64 *__restrict__ hist, u32 *__restrict__ count,
                                                                u64 *__restrict__ out) {
-    __shared__ u64 acc[129];
+    __shared__ u64 acc[kHistBins];
     const u32 t = threadIdx.x;
-    if (t < 129) acc[t] = 0;
+    if (t < kHistBins) acc[t] = 0;
     __syncthreads();
-    for (u32 e = t; e < kHistCopies * 129; e += blockDim.x) {
+    for (u32 e = t; e < kHistCopies * kHistBins; e += blockDim.x) {
         const u64 v = hist[e];
         if (v) {
-            atomicAdd((unsigned long long *)&acc[e % 129], (unsigned long long)v);
+            atomicAdd((unsigned long long *)&acc[e % kHistBins], (unsigned long long)v);
             hist[e] = 0;
         }
     }
     __syncthreads();
-    if (t < 129) out[t] = acc[t];
-    if (t == 129) {
-        out[129] = *count;
+    if (t < kHistBins) out[t] = acc[t];
+    if (t == kFinCount) {
+        out[kFinCount] = *count;
         *count = 0;
     }
 }

@@ -1089,7 +1089,7 @@ struct Fd2Args {
     // radix-B digits of start (xs) and tail (xt), least significant first,
     // for init_at (bases whose n passes 64 bits; kXDigits >= NX)
     u32 xs[12], xt[12];
-    u64 *hist;          // kHistCopies x 129 bins
+    u64 *hist;          // kHistCopies x kHistBins bins
     NumOut out;
     const uint4 *tabs;
     FieldFinish fin;    // fin.out_mapped == nullptr: no in-kernel finish
@@ -1115,14 +1115,14 @@ __device__ __forceinline__ void field_finish(const FieldFinish &fin, u64 *hist, 
     if (!last) return;
     FD2_STAMP_P(stamps, 7);  // the last workgroup: arrival known
     unsigned long long *acc = (unsigned long long *)smem;
-    for (u32 b = threadIdx.x; b < 129; b += WG) acc[b] = 0;
+    for (u32 b = threadIdx.x; b < kHistBins; b += WG) acc[b] = 0;
     __syncthreads();
     // All of a lane's loads issued before the first is used: one L2 round
     // trip for the copies instead of one per copy row.  Only bins < nbins
     // (base + 1) are read: the field's launches touch no other bin, and every
     // finish leaves the bins it read at zero (the generic kernel's finish
     // kernel zeroes all of them).
-    constexpr u32 PER = (kHistCopies * 129 + WG - 1) / WG;
+    constexpr u32 PER = (kHistCopies * kHistBins + WG - 1) / WG;
     const u32 NE = ncopies * nbins;
     const u32 nmiss = threadIdx.x == 0 ? __hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
     u64 v[PER];
@@ -1131,13 +1131,13 @@ __device__ __forceinline__ void field_finish(const FieldFinish &fin, u64 *hist, 
     for (u32 k = 0; k < PER; k++) {
         const u32 e = threadIdx.x + k * WG;
         const u32 c = e / nbins, b = e - c * nbins;
-        at[k] = c * 129 + b;
+        at[k] = c * kHistBins + b;
         v[k] = e < NE ? __hip_atomic_load(&hist[at[k]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
     }
 #pragma unroll
     for (u32 k = 0; k < PER; k++) {
         if (v[k]) {
-            atomicAdd(&acc[at[k] % 129], (unsigned long long)v[k]);
+            atomicAdd(&acc[at[k] % kHistBins], (unsigned long long)v[k]);
             __hip_atomic_store(&hist[at[k]], (u64)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
@@ -1151,15 +1151,15 @@ __device__ __forceinline__ void field_finish(const FieldFinish &fin, u64 *hist, 
         const u64 t = (u64)fin.tag << 32;
         for (u32 b = threadIdx.x; b < nbins; b += WG) fin.out_mapped[b] = t | (u32)acc[b];
         if (threadIdx.x == 0) {
-            fin.out_mapped[129] = t | nmiss;
+            fin.out_mapped[kFinCount] = t | nmiss;
             __hip_atomic_store(count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         FD2_STAMP_P(stamps, 9);
         return;
     }
-    for (u32 b = threadIdx.x; b < 129; b += WG) fin.out_mapped[b] = acc[b];
+    for (u32 b = threadIdx.x; b < kHistBins; b += WG) fin.out_mapped[b] = acc[b];
     if (threadIdx.x == 0) {
-        fin.out_mapped[129] = nmiss;
+        fin.out_mapped[kFinCount] = nmiss;
         __hip_atomic_store(count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // Publish: every lane's mapped stores complete, then one system-scope
@@ -1169,7 +1169,7 @@ __device__ __forceinline__ void field_finish(const FieldFinish &fin, u64 *hist, 
     __syncthreads();
     FD2_STAMP_P(stamps, 9);  // mapped stores complete
     if (threadIdx.x == 0)
-        __hip_atomic_store(&fin.out_mapped[130], fin.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&fin.out_mapped[kFinSeq], fin.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // One lane's chunk: `chunk` numbers from n0 (the state at n0 built by init;
@@ -1761,14 +1761,14 @@ __device__ __forceinline__ void fd2_load_tables(unsigned char *smem, const uint4
 }
 
 // A workgroup's end (after the barrier that follows its steps): the window
-// rows reduced and, with the out-of-window bins, added to row `row` (129 bins
+// rows reduced and, with the out-of-window bins, added to row `row` (kHistBins bins
 // apart) of hist_rows.
 template <class P>
 __device__ __forceinline__ void fd2_flush(const unsigned char *smem, u64 *hist_rows, u32 row_out, u32 tid) {
     const u32 *hist = (const u32 *)(smem + P::HB);
     const u32 *outl = (const u32 *)(smem + P::OUTL);
     const u32 lane = tid & 63, wave = tid >> 6;
-    u64 *hist_out = hist_rows + row_out * 129;
+    u64 *hist_out = hist_rows + row_out * kHistBins;
     // Window rows: wave w sums rows w, w + WG/64, ...; all of a wave's rows
     // are read and reduced together, so their cross-lane steps overlap.
     constexpr u32 NWAVE = P::WG / 64, RPW = (P::W + NWAVE - 1) / NWAVE;
@@ -1980,7 +1980,7 @@ __device__ __forceinline__ void fd2_body(const Fd2Args &a) {
     __syncthreads();
     FD2_STAMP(a, 4);  // every wave's steps done
     const u32 lane = tid & 63, wave = tid >> 6;
-    u64 *hist_out = a.hist + (blockIdx.x % a.ncopies) * 129;
+    u64 *hist_out = a.hist + (blockIdx.x % a.ncopies) * kHistBins;
     // Window rows: wave w sums rows w, w + WG/64, ...; all of a wave's rows
     // are read and reduced together, so their cross-lane steps overlap.
     constexpr u32 NWAVE = P::WG / 64, RPW = (P::W + NWAVE - 1) / NWAVE;
@@ -2050,7 +2050,7 @@ static_assert(sizeof(Fd2Unit) == 80, "descriptor layout");
 
 struct Fd2BatchArgs {
     const Fd2Unit *units;  // one per workgroup
-    u64 *hist;             // rows of 129 bins
+    u64 *hist;             // rows of kHistBins bins
     u32 ncopies;           // 0: row = the descriptor's; else blockIdx.x % ncopies (sum mode)
     u32 cutoff;
     NumOut out;
@@ -2108,7 +2108,7 @@ fd2_batch_kernel(Fd2BatchArgs a) {
     __syncthreads();
     if (active) walk_chunk<P>(st, smem, chunk, n0_lo, n0_hi, hbase, hinc, outl, cutoff, out, probe_acc);
     __syncthreads();
-    fd2_flush<P>(smem, a.hist, row, tid);  // row < 2^14 rows of a pass: row * 129 fits 32 bits
+    fd2_flush<P>(smem, a.hist, row, tid);  // row < 2^14 rows of a pass: row * kHistBins fits 32 bits
 }
 
 template <class P>

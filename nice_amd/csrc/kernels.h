@@ -1,12 +1,15 @@
 // kernels.h -- host-side launch entry points for the gfx950 kernels
 // (implemented in detailed.hip / niceonly.hip / niceonly_part.hip, used by
-// nice_abi.cpp).
+// the C ABI files, abi_*.cpp).  The word layouts host and device share are in
+// layout.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <vector>
+
+#include "layout.h"
 
 namespace nice {
 
@@ -18,22 +21,18 @@ struct NumOut {
     uint32_t cap;
 };
 
-// Detailed histograms live in kHistCopies copies of 129 u64 bins (summed by
-// the host); a workgroup flushes into copy blockIdx.x % kHistCopies.
-constexpr uint32_t kHistCopies = 64;
-
 // In-kernel end of a field (fd2 kernels): the launch's last workgroup sums
 // the histogram copies into out_mapped[0..128] (mapped host memory), writes
-// the near-miss count to out_mapped[129] and re-zeroes copies, count and
-// *done; then, after a system-scope release, seq to out_mapped[130], which the
+// the near-miss count to out_mapped[kFinCount] and re-zeroes copies, count and
+// *done; then, after a system-scope release, seq to out_mapped[kFinSeq], which the
 // host polls instead of waiting for the kernel's completion signal.
 // out_mapped == nullptr: the caller runs launch_detailed_finish.
 struct FieldFinish {
     uint64_t *out_mapped;
-    uint32_t *done;  // kDoneWords arrival counters (nice_device.hpp), re-zeroed by the finish
+    uint32_t *done;  // kDoneWords arrival counters (layout.h), re-zeroed by the finish
     uint64_t seq;    // the field's sequence number (nonzero)
     // Nonzero (fields of < 2^31 numbers): every result word is published as
-    // tag << 32 | value -- bins 0..base and the near-miss count [129] -- with
+    // tag << 32 | value -- bins 0..base and the near-miss count [kFinCount] -- with
     // no ordering among them and no sequence word; the host takes the field
     // as finished once every word carries the tag (one fewer round trip to
     // host memory than stores, wait, release store of the sequence word).
@@ -45,7 +44,7 @@ struct DetailedLaunch {
     uint64_t count;              // numbers in the segment
     uint32_t base;
     uint32_t cutoff;             // near-miss cutoff (number_stats.rs:15-17)
-    uint64_t *hist;              // kHistCopies x 129 u64 bins, accumulated
+    uint64_t *hist;              // kHistCopies x kHistBins u64 bins, accumulated
     uint32_t hist_copies;        // fd2: copies the field's launches use (set by launch_detailed_fd2)
     NumOut out;
     FieldFinish fin;             // fd2 only; see FieldFinish
@@ -87,7 +86,7 @@ struct BatchLaunch {
     const BatchUnit *units;  // host
     size_t n_units;
     void *h_desc, *d_desc;   // pinned staging / device array, n_units x kBatchDescBytes
-    uint64_t *hist;          // rows of 129 u64 bins (zeroed by the caller)
+    uint64_t *hist;          // rows of kHistBins u64 bins (zeroed by the caller)
     uint32_t ncopies;        // 0: unit.row selects the row; else workgroup b flushes into row b % ncopies
     NumOut out;
     uint32_t *launches;      // if set, incremented per kernel launch enqueued
@@ -103,7 +102,7 @@ void fd2_force_sib_stride(uint32_t L);
 // launchers accept a cutoff with cutoff + 1 >= w0 + w.
 bool fd2_window(uint32_t base, uint32_t *w0, uint32_t *w);
 // Field epilogue on the launch stream: out_mapped[0..128] = the summed
-// histogram copies, out_mapped[129] = *count; copies and counter are zeroed.
+// histogram copies, out_mapped[kFinCount] = *count; copies and counter are zeroed.
 hipError_t launch_detailed_finish(uint64_t *hist, uint32_t *count, uint64_t *out_mapped, hipStream_t s);
 // Generic per-n kernel: any base 2..128, any n < 2^128.
 hipError_t launch_detailed_generic(const DetailedLaunch &p, int num_cus, hipStream_t s);
@@ -122,14 +121,14 @@ struct Leaf {
 // workgroup copies the MSD counters (device MSD) and the nice count into
 // mapped host memory, so a field needs no copy launches.
 // Every candidate launch ends with its last workgroup re-zeroing the device
-// MSD's per-batch leaf-record count (counters[24]) for the next batch; the
+// MSD's per-batch leaf-record count (kMsdLeafCount) for the next batch; the
 // field's last launch instead copies the counters and the nice count out and
 // re-zeroes them for the slot's next field (no memset or copy launches).
 struct NiceFinish {
-    uint32_t *msd_mapped;          // 32 words (device MSD field end) or null
+    uint32_t *msd_mapped;          // kMsdMappedWords words (device MSD field end) or null
     uint32_t *count_mapped;        // nice count (field end) or null
     uint32_t *msd_counters;        // device MSD counters, or null (host MSD)
-    uint32_t *done;                // kDoneWords arrival counters (nice_device.hpp), re-zeroed;
+    uint32_t *done;                // kDoneWords arrival counters (layout.h), re-zeroed;
                                    // null: no epilogue
 };
 
@@ -157,7 +156,7 @@ struct SoundLaunch {
     const uint32_t *residues;     // StrideTable::residues_flagged (bit 31: the low digits repeat)
     const uint32_t *lowmask;      // StrideTable::lowmask, (base + 31) / 32 words per residue
     LeafMask *leaf_masks;         // device MSD: parallel to MsdLaunch::leaves
-    unsigned long long *rejected; // candidates the prefix test rejected (counters[96..97], sticky)
+    unsigned long long *rejected; // candidates the prefix test rejected (counters + kMsdRejected, sticky)
     uint32_t fast;                // the field runs the base's compile-time sound variants
                                   // (sound_prefix_field), else the run-time-base ones
     uint32_t prefix_test;         // 0: the recursion without Filter C only (fields that are not
@@ -193,14 +192,7 @@ struct MsdLaunch {
     uint64_t chunk;               // MSD chunk size (client rule)
     uint64_t floor_size;          // recursion floor (250)
     MsdNode *q[2];                // ping-pong level queues
-    uint32_t *counters;           // [0..23] level sizes, [24] leaf records (batch), [25]
-                                  // overflow flag, [26] MSD-surviving ranges (sticky),
-                                  // [27] square survivors (written at the field's end),
-                                  // [28..29] u64 candidates, [30..31] u64 numbers inside
-                                  // the ranges (sticky); [32..95] square-survivor partial
-                                  // counts (workgroup b adds to 32 + b % 64, sticky);
-                                  // [96..97] u64 candidates rejected by the sound filter's
-                                  // prefix test (sticky, copied out to mapped words 32..33)
+    uint32_t *counters;           // kMsdCounterWords words, laid out as layout.h describes
     uint32_t q_cap;
     Leaf *leaves;
     uint32_t leaf_cap;
@@ -214,11 +206,6 @@ struct MsdLaunch {
     uint32_t probe;               // probe build only (NICE_MSD_PROBE): 1 no skip test, 2 no leaf stride math,
                                   // 4 wave kernel: no candidate test
 };
-constexpr uint32_t kMsdCounterWords = 98;
-constexpr uint32_t kMsdMappedWords = 34;
-// A leaf's candidate count is capped at kLeafPiece: longer runs are stored as
-// several leaves, so niceonly_kernel's per-wave sums of 8 leaves fit 32 bits.
-constexpr uint32_t kLeafPiece = 1u << 28;
 // Node of a chunk's fused recursion: offset from the chunk start, size.
 struct ChunkNode {
     uint32_t off, size;

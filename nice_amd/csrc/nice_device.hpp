@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "layout.h"
+
 namespace nice {
 
 typedef uint32_t u32;
@@ -211,9 +213,9 @@ static inline GenericBase make_generic(u32 base) {
 // the niceonly kernel's ~2000 mostly idle ones ~80 us.  Every add is an
 // agent-scope RMW whose result the next one waits for, so the chain orders
 // the hand-off like a single counter (MI355X_MICROARCH.md, inter-workgroup
-// visibility).  done[] has kDoneWords words; the last workgroup re-zeroes
-// them with done_reset().  Called by thread 0; returns true in the last one.
-constexpr uint32_t kDoneGroups = 64, kDoneWords = kDoneGroups + 1;
+// visibility).  done[] has kDoneWords words (layout.h); the last workgroup
+// re-zeroes them with done_reset().  Called by thread 0; returns true in the
+// last one.
 __device__ __forceinline__ bool last_block_arrive(uint32_t *done) {
     const uint32_t g = blockIdx.x % kDoneGroups, n = gridDim.x;
     // small grids: one counter (saves an L2 round trip on the critical path;

@@ -29,12 +29,13 @@ __global__ void msd_init_kernel(MsdLaunch p) {
         const u64 size = rem_hi || rem_lo > p.chunk ? p.chunk : rem_lo;
         p.q[0][i] = MsdNode{c * p.chunk, size};
     }
-    // counters: [0] level-0 size, [1..24] per batch, [25..31] sticky over the
-    // field (zeroed with the first batch, as is the field's nice count)
-    if (blockIdx.x == 0 && threadIdx.x < 32) {
+    // counters (layout.h): [0] level-0 size, up to kMsdLeafCount per batch,
+    // the rest sticky over the field (zeroed with the first batch, as is the
+    // field's nice count)
+    if (blockIdx.x == 0 && threadIdx.x < kMsdSquareParts) {
         const u32 w = threadIdx.x;
         if (w == 0) p.counters[0] = (u32)p.nchunks;
-        else if (w < 25 || p.first_batch) p.counters[w] = 0;
+        else if (w <= kMsdLeafCount || p.first_batch) p.counters[w] = 0;
         if (w == 0 && p.first_batch) *p.nice_count = 0;
     }
 }

@@ -7,7 +7,8 @@
 //   * the device kernels (niceonly_kernels.hpp, instantiated per part in
 //     niceonly_part.hip: ConstBase divisors, radix_fast.hpp's in-range limb
 //     paths, the square-survivor queue, the LDS pair table, the lane walk);
-//   * the ABI hooks and nice_niceonly_fast_base (nice_abi.cpp);
+//   * the ABI hooks (abi_hooks.cpp) and nice_niceonly_fast_base
+//     (abi_context.cpp);
 //   * the host paths' compile-time divisors (cpu_path.cpp with_base,
 //     host_math.hpp make_msd).
 // tests/test_niceonly_bases.py checks the list against its definition.

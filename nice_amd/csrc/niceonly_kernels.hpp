@@ -306,12 +306,12 @@ __device__ __forceinline__ void cand_flush(const NiceonlyLaunch &p, CandWave &cw
 }
 
 // This workgroup's square survivors (every wave's cube-queue total) into the
-// field's partial counts (counters[32 + b % 64]): one LDS add per wave, one
+// field's partial counts (kMsdSquareParts, layout.h): one LDS add per wave, one
 // global add per workgroup.  Every thread calls it (a barrier inside).
 __device__ __forceinline__ void square_ok_flush(u32 *ctr, u32 *wg_sum, u32 waves_total, u32 lane) {
     if (lane == 0 && waves_total) atomicAdd(wg_sum, waves_total);
     __syncthreads();
-    if (threadIdx.x == 0 && ctr && *wg_sum) atomicAdd(&ctr[32 + blockIdx.x % 64], *wg_sum);
+    if (threadIdx.x == 0 && ctr && *wg_sum) atomicAdd(&ctr[kMsdSquareParts + blockIdx.x % kMsdSquarePartCount], *wg_sum);
 }
 
 // End of a niceonly launch (every thread of the workgroup calls it): the last
@@ -321,8 +321,8 @@ __device__ __forceinline__ void square_ok_flush(u32 *ctr, u32 *wg_sum, u32 waves
 // (count_mapped set): the MSD counters and the nice count out, then re-zeroed
 // for the slot's next field.  Batch end: only the per-batch leaf-record count
 // is re-zeroed, for the next batch.
-// SOUND: the prefix test's rejected count (counters[96..97]) goes out to mapped
-// words 32..33 and is re-zeroed with the rest.
+// SOUND: the prefix test's rejected count (kMsdRejected) goes out to mapped
+// words kMsdMappedRejected, +1 and is re-zeroed with the rest.
 template <bool SOUND = false>
 __device__ __forceinline__ void nice_launch_finish(const NiceFinish &fin, u32 *count) {
     __shared__ u32 last;
@@ -334,21 +334,22 @@ __device__ __forceinline__ void nice_launch_finish(const NiceFinish &fin, u32 *c
     u32 *ctr = fin.msd_counters;
     const u32 w = threadIdx.x;
     if (fin.count_mapped) {
-        if (ctr && w < 64) {  // wave 0
-            // the square-survivor partials summed into word 27, then re-zeroed
-            u32 part = __hip_atomic_load(&ctr[32 + w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&ctr[32 + w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (ctr && w < kMsdSquarePartCount) {  // wave 0
+            // the square-survivor partials summed into kMsdSquareOk, then re-zeroed
+            u32 part = __hip_atomic_load(&ctr[kMsdSquareParts + w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&ctr[kMsdSquareParts + w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
             for (int o = 32; o >= 1; o >>= 1) part += __shfl_xor(part, o);
-            if (w < 32) {
+            if (w < kMsdSquareParts) {
                 const u32 v = __hip_atomic_load(&ctr[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                fin.msd_mapped[w] = w == 27 ? part : v;
-                if (w >= 24) __hip_atomic_store(&ctr[w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                fin.msd_mapped[w] = w == kMsdSquareOk ? part : v;
+                if (w >= kMsdLeafCount) __hip_atomic_store(&ctr[w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             if constexpr (SOUND) {
-                if (w >= 32 && w < 34) {
-                    fin.msd_mapped[w] = __hip_atomic_load(&ctr[64 + w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&ctr[64 + w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (w >= kMsdMappedRejected && w < kMsdMappedWords) {
+                    u32 *rej = &ctr[kMsdRejected - kMsdMappedRejected + w];
+                    fin.msd_mapped[w] = __hip_atomic_load(rej, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(rej, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
         }
@@ -356,8 +357,8 @@ __device__ __forceinline__ void nice_launch_finish(const NiceFinish &fin, u32 *c
             *fin.count_mapped = __hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-    } else if (ctr && w == 24) {
-        __hip_atomic_store(&ctr[24], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else if (ctr && w == kMsdLeafCount) {
+        __hip_atomic_store(&ctr[kMsdLeafCount], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     done_reset(fin.done);
 }
@@ -688,10 +689,10 @@ __device__ __forceinline__ void append_leaf(const MsdLaunch &p, u32 act, u64 lo,
     }
     const u64 pieces64 = act == 1 ? (ld.count + kLeafPiece - 1) / kLeafPiece : 0;
     const u32 pieces = pieces64 > 0xffffu ? 0xffffu : (u32)pieces64;
-    const u32 pos = block_reserve(&p.counters[24], pieces, slots);
+    const u32 pos = block_reserve(&p.counters[kMsdLeafCount], pieces, slots);
     if (act != 1) return;
     if (pieces64 > 0xffffu || (u64)pos + pieces > p.leaf_cap) {
-        atomicOr(&p.counters[25], 1u);
+        atomicOr(&p.counters[kMsdOverflow], 1u);
     } else {
         u64 b0_lo = ld.b0_lo, b0_hi = ld.b0_hi;
         u64 gi = ld.g0;  // residue-sequence index relative to b0
@@ -728,9 +729,9 @@ __device__ __forceinline__ void flush_stats(const MsdLaunch &p, u64 n_st, u64 c_
     }
     __syncthreads();
     if (threadIdx.x == 0 && stat[0]) {
-        atomicAdd(&p.counters[26], (u32)stat[0]);
-        atomicAdd((unsigned long long *)(p.counters + 28), stat[1]);
-        atomicAdd((unsigned long long *)(p.counters + 30), stat[2]);
+        atomicAdd(&p.counters[kMsdRanges], (u32)stat[0]);
+        atomicAdd((unsigned long long *)(p.counters + kMsdCandidates), stat[1]);
+        atomicAdd((unsigned long long *)(p.counters + kMsdNumbers), stat[2]);
     }
 }
 
@@ -770,7 +771,7 @@ msd_level_kernel(MsdLaunch p, u32 level, G g, S... snd) {
         const u32 cpos = block_reserve(&p.counters[level + 1], act == 2 ? 2u : 0u, slots);
         if (act == 2) {
             if (cpos + 1 >= p.q_cap) {
-                atomicOr(&p.counters[25], 1u);
+                atomicOr(&p.counters[kMsdOverflow], 1u);
             } else {
                 const u64 half = nd.size / 2;
                 qout[cpos] = MsdNode{nd.off, half};
@@ -836,7 +837,7 @@ msd_fused_kernel(MsdLaunch p, ChunkNode *scratch, u32 cap, G g, S... snd) {
                 if (act == 2) {
                     const u32 cp = atomicAdd(&cnt[1], 2u);
                     if (cp + 2 > cap) {
-                        atomicOr(&p.counters[25], 1u);
+                        atomicOr(&p.counters[kMsdOverflow], 1u);
                     } else {
                         const u32 half = nd.size / 2;
                         qout[cp] = ChunkNode{nd.off, half};
@@ -1063,7 +1064,7 @@ msd_wave_kernel(MsdLaunch p, NiceonlyLaunch c, u32 level0, StackNode *scratch, G
 
     // Leaves the BFS levels above produced (clipped or depth-limited nodes):
     // already stride descriptors in the batch's leaf list.
-    const u32 n_list = min(p.counters[24], p.leaf_cap);
+    const u32 n_list = min(p.counters[kMsdLeafCount], p.leaf_cap);
     for (u64 b = gwave * kLeafGroup; b < n_list; b += nwaves * kLeafGroup) {
         Leaf lf{0, 0, 0, 0};
         if (lane < kLeafGroup && b + lane < n_list) lf = p.leaves[b + lane];
@@ -1135,7 +1136,7 @@ msd_wave_kernel(MsdLaunch p, NiceonlyLaunch c, u32 level0, StackNode *scratch, G
         const u64 bs = __ballot(act == 2);
         const u32 nsplit = (u32)__popcll(bs);
         if (sp + 2 * nsplit > kStackCap) {
-            if (lane == 0) atomicOr(&p.counters[25], 1u);  // reported as an error by the host
+            if (lane == 0) atomicOr(&p.counters[kMsdOverflow], 1u);  // reported as an error by the host
         } else {
             if (act == 2) {
                 const u32 r = sp + 2 * lane_rank(bs), half = nd.size / 2;

@@ -1,6 +1,6 @@
 # Host-code sanitizer runs (CPU only, this container): the CPU API
 # (cpu_path.cpp), the host hooks of host_math.hpp / radix_fast.hpp exported by
-# nice_abi.cpp, the no-device error paths and the oracle's pthread driver,
+# abi_hooks.cpp, the no-device error paths and the oracle's pthread driver,
 # built with ASan + UBSan and with TSan (make ... sanitize) and exercised by
 # the CPU test files, each run with the matching clang runtime preloaded into
 # the Python process.  Exit status: non-zero on any sanitizer report (the
