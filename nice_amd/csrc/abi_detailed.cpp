@@ -29,7 +29,7 @@ int enqueue_detailed(Device &d, Slot &sl, u128 s, u128 e, uint32_t base, bool *f
     p.sib = sl.sib;
     // Another detailed field of this device submitted and not yet collected:
     // the caller pipelines, so this field's launches are shaped for throughput
-    // (launch_sib).  Whether that field is still running does not matter --
+    // (fd2_plan.hpp plan_sib).  Whether that field is still running does not matter --
     // fields on the slot streams progress together and often finish
     // together, and a pick that followed their completion flipped every third
     // 2.5e8 field to the lone-field stride (8 % slower per step,

@@ -6,8 +6,8 @@
 #include <map>
 #include <mutex>
 
-#include "fd2_kernel.hpp"
 #include "fd2_combos.h"
+#include "fd2_launch.hpp"
 
 namespace nice {
 namespace fd2 {
@@ -199,10 +199,10 @@ uint32_t fd2_batch_wg(uint32_t base) {
     return (fd2::valu_limbs((int)base) & 1024) ? (uint32_t)fd2::big_wg((int)base) : 512u;
 }
 
-// The base's TCHUNK (Cfg), made odd as launch_cfg makes its chunks: odd chunks
-// spread a wave's low-digit entries over distinct bank pairs, and are never a
-// multiple of 16 (the bases without a low-digit table).
-uint32_t fd2_batch_chunk(uint32_t base) { return (base <= 45 ? 80u : (base <= 58 ? 160u : 240u)) + 1; }
+// The base's TCHUNK (Cfg), made odd as rounds_chunk makes its chunks: odd
+// chunks spread a wave's low-digit entries over distinct bank pairs, and are
+// never a multiple of 16 (the bases without a low-digit table).
+uint32_t fd2_batch_chunk(uint32_t base) { return (uint32_t)fd2::tchunk_of((int)base) + 1; }
 
 void fd2_batch_plan(uint32_t base, u128 a, u128 e, uint32_t row, std::vector<BatchUnit> &out) {
     const fd2::BaseThresholds &t = fd2::thresholds(base);
@@ -211,16 +211,9 @@ void fd2_batch_plan(uint32_t base, u128 a, u128 e, uint32_t row, std::vector<Bat
         const u128 stop = i < t.cuts.size() && t.cuts[i] < e ? t.cuts[i] : e;
         if (stop <= a) continue;
         const u128 cnt = stop - a;
-        // Whole workgroups of chunks <= the base's target, as launch_cfg's
-        // whole rounds: the fewest workgroups that hold the piece, then the
-        // chunk that fills them (so the last main workgroup is nearly full).
-        // A piece of <= WG numbers is one workgroup of one number per lane (a
-        // lane's steps are the latency of a small range).
-        const u128 nwg = (cnt + (u128)wg * tchunk - 1) / ((u128)wg * tchunk);
-        u64 chunk = (u64)((cnt + nwg * wg - 1) / (nwg * wg));
-        if (chunk > 1 && chunk % 2 == 0) chunk++;  // <= tchunk, which is odd
-        u128 units = cnt / chunk;  // lanes of `chunk` numbers
-        const u64 tail = (u64)(cnt - units * chunk);
+        const fd2::BatchTile tile = fd2::batch_tile(cnt, wg, tchunk);
+        const u64 chunk = tile.chunk, tail = tile.tail;
+        u128 units = tile.units;
         u128 n = a;
         while (units) {
             const u64 lanes = units < wg ? (u64)units : wg;
@@ -238,7 +231,7 @@ hipError_t launch_detailed_fd2_batch(const BatchLaunch &p, hipStream_t s) {
     const fd2::BaseThresholds &t = fd2::thresholds(p.base);
     const size_t nc = t.combos.size();
     const u32 B = p.base * p.base;
-    const int dn = p.base % 5 == 0 ? p.base / 5 : p.base / 5 + 1, nx = (dn + 1) / 2;  // Cfg::DN, NX
+    const int dn = fd2::digits_of((int)p.base).dn, nx = cdiv(dn, 2);  // Cfg::DN, NX
     // init_at reads the digits only where n passes 64 bits and the kernel
     // keeps 32-bit init columns (Cfg::N64, C64)
     const bool digits = !fd2::fits64(p.base, dn) && fd2_batch_wg(p.base) < 1024;

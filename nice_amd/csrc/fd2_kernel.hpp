@@ -1,6 +1,8 @@
 // fd2_kernel.hpp -- production finite-difference detailed kernel (gfx950):
-// the device code and its per-instantiation launcher.  Instantiated per base
-// by fd2_part*.hip (compiled in parallel), driven by fd2_detailed.hip.
+// the device code.  Its compile-time configuration is fd2_cfg.hpp, the
+// launch planning fd2_plan.hpp, the per-instantiation launchers
+// fd2_launch.hpp.  Instantiated per base by fd2_part*.hip (compiled in
+// parallel), driven by fd2_detailed.hip.
 //
 // Computes exactly what process_range_detailed does (common/src/
 // client_process.rs:150-191: per n the unique-digit count of n^2 and n^3 in
@@ -46,467 +48,13 @@
 // per wave-step; see DESIGN.md §3.1 for the cycle model and the measured
 // roofline.
 #pragma once
-#include <stdlib.h>
-
-#include <algorithm>
-#include <atomic>
-#include <cmath>
-#include <map>
-#include <tuple>
-#include <mutex>
-#include <type_traits>
-
-#include "host_math.hpp"
+#include "fd2_cfg.hpp"
 #include "kernels.h"
 #include "nice_device.hpp"
 #include "probe.hpp"
 
 namespace nice {
 namespace fd2 {
-
-constexpr int log2ceil(unsigned v) { int t = 0; while ((1u << t) < v) t++; return t; }
-constexpr int ilog2(unsigned v) { int t = 0; while ((2u << t) <= v) t++; return t; }
-
-// Exactness of the digit split q = mulhi(ES v, m) = v / b over v < b^2.
-constexpr bool split_exact(unsigned base, unsigned es, unsigned long long m) {
-    for (unsigned v = 0; v < base * base; v++)
-        if (((unsigned long long)es * v * m) >> 32 != v / base) return false;
-    return true;
-}
-
-// Tuning / bottleneck-probe knobs read from the environment exist only in
-// the probe build (make -C nice_amd probe -> libnice_hip_probe.so, used by
-// scripts/); the product library ignores the environment and always runs the
-// production configuration.
-
-// Histogram window [W0, W0 + W) per base: where the unique-count
-// distribution of in-range n lives (scripts/fd2_windows.py, 40 000 samples
-// per base: at most 6e-4 of n fall outside; b40/50/80 keep their measured
-// production windows).  W0 + W <= cutoff + 1: every near-miss is outside.
-constexpr int window_w(int b) {
-    return b == 40 ? 15 : b == 50 ? 18 : b == 80 ? 28 : b <= 45 ? 15 : b <= 61 ? 18 : b <= 70 ? 20 : 28;
-}
-constexpr int window_w0(int b) {
-    switch (b) {
-    case 40: return 18;
-    case 42: return 19;
-    case 43: return 20;
-    case 44: case 45: case 47: return 21;
-    case 48: return 22;
-    case 49: return 23;
-    case 50: return 21;
-    case 52: return 24;
-    case 53: return 25;
-    case 54: case 55: return 26;
-    case 57: return 27;
-    case 58: return 28;
-    case 59: case 60: return 29;
-    case 62: case 63: return 30;
-    case 64: return 31;
-    case 65: return 32;
-    case 67: return 33;
-    case 68: return 34;
-    case 80: return 33;
-    default: return b * 61 / 100 - window_w(b) / 2;
-    }
-}
-
-// Waves per SIMD whose VGPR budget (512 / waves) holds a base's lane state
-// without spilling in the step loop: the stepped and cached limbs of n^2, n^3,
-// 2n+1, 3n+1 plus the mask words, R = NS + NC + 2 NX + 1 + MW registers, and
-// about as many temporaries.  b40 (R = 31) just fits 64 VGPRs (8 waves);
-// R = 35..38 (b42..50) needs ~80 (6 waves), R <= 46 (b52..60) ~96 (5),
-// wider bases 128 (4).
-constexpr int state_regs(int base) {
-    const int k = base / 5, r5 = base % 5;
-    const int d2 = r5 == 0 ? 2 * k : (r5 == 4 ? 2 * k + 2 : 2 * k + 1);
-    const int d3 = r5 == 0 ? 3 * k : (r5 == 2 ? 3 * k + 1 : 3 * k + 2);
-    const int dn = r5 == 0 ? k : k + 1;
-    return (d2 + 1) / 2 + (d3 + 1) / 2 + 2 * ((dn + 1) / 2) + 1 + (base + 31) / 32;
-}
-constexpr int state_waves(int base) {
-    const int r = state_regs(base);
-    return r <= 31 ? 8 : (r <= 38 ? 6 : (r <= 46 ? 5 : 4));
-}
-
-// In-range n fits 64 bits: BASE^DN <= 2^64 (DN digits).
-constexpr bool fits64(unsigned base, int digits) {
-    unsigned long long v = 1;
-    for (int i = 0; i < digits; i++) {
-        if (v > ~0ull / base) return false;
-        v *= base;
-    }
-    return true;
-}
-
-// Limbs decoded by VALU instead of a table lookup (Cfg::VD: top C limbs +
-// 16 x top S limbs), per base where the lookups' bank conflicts outweigh the
-// VALU work: the best of VD 0/1/2/3/17 on the 1e9 field at the range start
-// (scripts/vd_sweep_all.py, profiles/r02/vd_sweep_all.log), kept where it
-// gains over ~1 %; without a low-digit table also limb 0 (VD & 256,
-// profiles/r02/vd_sweep_low.log).  b64: 6.31 -> 4.25 ms (its table index
-// n^2 mod 4096 keeps few residues mod 32, so lookups pile onto few banks);
-// b45 2.60 -> 2.41; b60 3.79 -> 3.41; b63 3.96 -> 3.70; b68 7.42 -> 6.87;
-// b80 8.22 -> 7.46; b40 neutral (r01).  Re-swept on the persistent grid
-// (profiles/r03/vd_sweep_persistent.log): b55 0 -> 1 (2.91 -> 2.87 ms), b58
-// 1 -> 2 (3.08 -> 3.00); every other base within ~1 % of its choice.
-constexpr int valu_limbs(int base) {
-    switch (base) {
-    case 43: case 44: case 45: case 48: case 50: case 54: case 55: return 1;
-    case 53: case 58: case 65: return 2;
-    case 67: case 68: case 80: return 256;  // limb 0 by VALU
-    // b59..64: the low-digit table with its carries in a side table (VD &
-    // 1024, Cfg::LSDX), then the best top limbs by VALU: b59 3.31 -> 3.01 ms,
-    // b60 3.39 -> 3.18, b62 3.49 -> 3.35, b63 3.71 -> 3.59, b64 4.17 -> 4.13
-    // (profiles/r03/lsdx_sweep.log)
-    case 59: case 63: case 64: return 1024 + 2;
-    case 60: return 1024 + 17;
-    case 62: return 1024 + 1;
-    default: return 0;
-    }
-}
-
-// Fields of >= 1e7 on the three-mask-word bases (b65..80, the persistent
-// 1024-thread kernel): limb 0 by VALU and the VALU-decoded C limbs just BELOW
-// the top stepped one (VD & 2048, Cfg::VDB).  The top stepped limb only takes
-// carries, so across a wave its lookup is nearly a broadcast (4 LDS cycles on
-// b80's index pattern against 11-12 for the limbs below it,
-// scripts/ubench/lds_trace_gen.py), and decoding it by VALU saved little;
-// decoding the limbs below it saves full-price lookups.  How many: per limb
-// layout (the segment's ND, NE), from interleaved A/B sweeps over 1e9 fields
-// at several points of each range with the select-free decode of or_valu and
-// the one-multiply C carry (profiles/r04/vd_below_top.log): three, four where
-// b80's n^3 has 17 limbs.  Against the round-3 kernels: b80 1e9 6.84 -> 6.24
-// ms at the range start, b65 5.97 -> 5.43, b67 5.94 -> 5.64, b68 6.48 -> 5.57.
-// The two-word bases (co-bound by VALU and LDS) move their VALU-decoded
-// limbs below the top where that measured faster at both points of the
-// range: b50 -1.1 / -2.2 %, b53 -1.1 / -1.4, b60 -1.2 / -1.7 (same VALU work,
-// cheaper lookups); elsewhere within +-1 % or mixed, unchanged.  b40 (no
-// VALU-decoded limbs before) decodes one C limb below the top on its 8-limb
-// n^3 layouts (the first ~45 % of the range, the extra-large benchmark field
-// among them): 2.03 -> 1.98 ms at the range start, 2.74 -> 2.62 at 0.1, 2.22
-// -> 2.17 at 0.3, and it beats one or two more decoded limbs at every point
-// checked in 0.02..0.35; on the 9-limb layout it lost 0-2 % and stays as it
-// was (profiles/r04/vd_b40.log).
-constexpr int valu_limbs_big(int base, int nd, int ne) {
-    if (base == 40) return ne == 8 ? 2048 | 1 : 0;
-    if (base == 50 || base == 53 || base == 60) return valu_limbs(base) | 2048;
-    if ((base + 31) / 32 != 3) return valu_limbs(base);
-    if (base == 80 && ne == 17) return 256 | 2048 | 4;
-    return 256 | 2048 | 3;
-}
-
-// LDS bytes / waves per SIMD of a base's kernel at a workgroup size (the
-// formulas of Cfg, evaluated without instantiating it).
-constexpr int lds_bytes(int base, int wg) {
-    const int mw = (base + 31) / 32, b2 = base * base;
-    const bool split = mw == 3 && (valu_limbs(base) & 512) != 0;
-    const int es = mw == 1 ? 4 : (mw == 2 || split ? 8 : 16);
-    int t = 0;
-    while ((1 << t) < b2) t++;
-    const int ebt = es * ((1 << t) - b2);
-    if (split) {  // [OUTL | X2 | X1 | window rows] (Cfg::SPLIT)
-        const int a = (4 * (base + 1) + 15) / 16 * 16, h = (ebt / 2 + 15) / 16 * 16;
-        const int t2 = a > h ? a : h;
-        const int tb0 = (t2 + 4 * b2 + 15) / 16 * 16, tbe = (ebt + 15) / 16 * 16;
-        const int tb = tb0 > tbe ? tb0 : tbe;
-        return (tb + b2 * es + 15) / 16 * 16 + window_w(base) * (wg / 2) * 4;
-    }
-    const int tb0 = (window_w(base) * (wg / 2) * 4 + 4 * (base + 1) + 15) / 16 * 16;
-    const int tb = tb0 >= ebt ? tb0 : (ebt + 15) / 16 * 16;
-    const int db = base - 32;
-    const bool lsd_w1 = mw == 2 && db > 0 && db + (db > 20 ? 4 : 10) <= 30;
-    const bool lsdx = mw == 2 && db > 0 && !lsd_w1 && (valu_limbs(base) & 1024) != 0;
-    return tb + (b2 * es + 15) / 16 * 16 + (lsd_w1 || lsdx ? (2 * b2 * es + 15) / 16 * 16 : 0) +
-           (lsdx ? (2 * b2 + 15) / 16 * 16 : 0);
-}
-// Waves per SIMD actually resident: the LDS and VGPR caps, in whole
-// workgroups (a workgroup puts wg / 256 waves on each SIMD).
-constexpr int waves_at(int base, int wg) {
-    const int lds = (163840 / lds_bytes(base, wg)) * (wg / 64) / 4;
-    const int cap = lds < state_waves(base) ? lds : state_waves(base);
-    return cap / (wg / 256) * (wg / 256);
-}
-// Workgroup size for fields >= 1e7 in rounds of workgroups: the kernels are
-// bound by LDS lookups and want as many in flight as fit, so the size with
-// more waves per SIMD under the LDS budget wins, 512 on a tie.  Measured on
-// the first three bases: b40 two 1024-thread workgroups per CU (8 waves/SIMD)
-// 2.38 ms vs 2.43 for three 512-thread ones (6 waves,
-// profiles/r01/fd2_wg_sweep2.log); b80 one 1024-thread workgroup (4 waves)
-// 8.47 ms vs 9.37 at 512 (2 waves, profiles/r01/b80_wg_sweep.log); b50 4
-// waves either way, 512 kept.
-constexpr int rounds_wg(int base) { return waves_at(base, 1024) > waves_at(base, 512) ? 1024 : 512; }
-// With the persistent grid (Cfg::PERS) a tie goes to 1024: one 1024-thread
-// workgroup per CU walking strided batches beats two 512-thread ones in
-// rounds on every such base (b42..50 -3..-10 %, b59..64 -2..-5 % per 1e9,
-// profiles/r03/pers_sweep_wg1024.log).
-constexpr int big_wg(int base) { return waves_at(base, 1024) >= waves_at(base, 512) ? 1024 : 512; }
-
-// Persistent grid by default where the kernel holds ONE workgroup per CU
-// (b52..58, b65..68, b80 at 1024 threads): with two or more, a workgroup's
-// draining tail overlaps another's steps, and rounds of workgroups win
-// (profiles/r03/pers_sweep_all.log: b52..58 -12..-15 %, b65..68 / b80 -6..-10 %
-// per 1e9; b42..50 and b59..64, two workgroups per CU, +1..+6 %).
-constexpr bool one_wg_per_cu(int base, int wg) { return waves_at(base, wg) == wg / 256; }
-
-// Sibling lanes (Cfg::SIB = M > 1): registers per wave for M lanes' state
-// (the shared limb-1 state once, the upper limbs of every sibling).
-constexpr int sib_waves(int base, int m) { return m <= 1 ? state_waves(base) : (m <= 3 ? 6 : 5); }
-
-template <int BASE_, int ND_, int NE_, int NE2_, int PROBE_ = 0, int WG_ = 512, int VD_ = 0, int LG_ = -1,
-          int PERS_ = -1, int SIB_ = 1>
-struct Cfg {
-    static constexpr int BASE = BASE_;
-    // Bottleneck probes (timing experiments only, results are wrong): 1 = no
-    // table lookups (limb words OR-ed directly), 2 = no LDS histogram add,
-    // 4 = no limb-1 lookups of S and C.
-    static constexpr int PROBE = PROBE_;
-    static constexpr int ND = ND_, NE = NE_, NE2 = NE2_;
-    static constexpr int k = BASE / 5, r5 = BASE % 5;
-    // Digit counts inside the valid range (base_range.rs:14-32).
-    static constexpr int D2 = r5 == 0 ? 2 * k : (r5 == 4 ? 2 * k + 2 : 2 * k + 1);
-    static constexpr int D3 = r5 == 0 ? 3 * k : (r5 == 2 ? 3 * k + 1 : 3 * k + 2);
-    static constexpr int DN = r5 == 0 ? k : k + 1;
-    static constexpr bool N64 = fits64(BASE, DN);  // init's u64 path
-    // init's products in u64 columns (the 1024-thread kernels of the bases
-    // whose n passes 64 bits: the register allocation that spills least);
-    // elsewhere u32 columns (every FD base's column sums fit 32 bits:
-    // static_assert below), normalised by 32-bit multiply-highs
-    // VD & 65536 (probe A/B): the round-5 init -- init_digits on the 128-bit n
-    // and u64 columns -- also on the 512-thread kernels of the bases whose n
-    // passes 64 bits; the persistent-grid probe configurations at 512
-    // threads (PERS_ = 1) take it too, their init being the round-5 one
-    static constexpr bool OLDINIT = (VD_ & 65536) != 0;
-    static constexpr bool C64 = !N64 && (WG_ >= 1024 || OLDINIT || PERS_ > 0);
-    static constexpr int NS = cdiv(D2, 2), NC = cdiv(D3, 2), NX = cdiv(DN, 2);
-    static constexpr int SL = ND + 1, CL = NE + 1, EL = NE2 + 1;  // per-step limbs
-    static constexpr int S_TOPD = D2 - 2 * (NS - 1), C_TOPD = D3 - 2 * (NC - 1);
-    static constexpr u32 B = (u32)BASE * BASE;
-    static constexpr int T = log2ceil(B);
-    static constexpr u32 BT = (1u << T) - B;
-    static constexpr int MW = (BASE + 31) / 32;
-    // VD & 512 (three mask words, b65..68 / b80): the digit-pair masks SPLIT
-    // into X1, 8-byte entries of the digits 0..63 (ds_read_b64), and X2, 4-byte
-    // entries of the digits 64.. (ds_read_b32), each table at its own entry
-    // size, so both spread a lane group over all 64 banks: the stored limb
-    // (scaled by 8) addresses X1 directly and X2 after one shift.  Probe
-    // only: on the kernel's own b80 index pattern b64 + b32 costs 11.9 LDS
-    // cycles per wave-lookup against 11.45 for one b128 of a 16-byte entry
-    // (scripts/ubench/lds_trace.hip, profiles/r04/lds_trace.log), and the
-    // kernel is 7 % slower with it.
-    static constexpr bool SPLIT = MW == 3 && (VD_ & 512) != 0;
-    static constexpr int ES = MW == 1 ? 4 : (MW == 2 || SPLIT ? 8 : 16);  // table entry stride (bytes)
-    static constexpr int SH = T + ilog2(ES);                     // carry bit of a scaled limb
-    static constexpr u32 ESB = ES * B, EBT = ES * BT;
-    static constexpr int WG = WG_;
-    // Target chunk (numbers per lane), see launch_cfg: a lane's init costs a
-    // few steps, more for wider bases.
-    static constexpr int TCHUNK = BASE <= 45 ? 80 : (BASE <= 58 ? 160 : 240);
-    static constexpr int NBINS = BASE + 1;
-    // Histogram window [W0, W0 + W): per-thread counters (u32, or u16 halves
-    // shared by threads t and t + WG/2 when LDS is tight).
-    static constexpr int W = window_w(BASE);
-    static constexpr int W0 = window_w0(BASE);
-    // Window counters: HQ per dword (u16 halves shared by threads t and
-    // t + WG/2).
-    static constexpr int HQ = 2;
-    static constexpr int HROW = WG / HQ;  // counters per window row
-    // (A branch-free window count -- every count to row min(uw, W), a dummy
-    // row W, out-of-window counts recorded behind one wave-uniform branch --
-    // measured 1 % slower on the b40 sibling kernel; skipping the
-    // out-of-window work altogether, wrong by design, only 3 % faster:
-    // profiles/r06/occupancy_ab.txt, bfw_uniform_branch_ab.log.)
-    static constexpr int HIST_BYTES = W * HROW * 4;
-    // Layout.  Default: [window rows | out-of-window bins (OUTL) | tables].
-    // The digit-pair table needs at least EBT below it: S limbs are stored
-    // biased by EBT and looked up at (TB - EBT) + S, an unsigned immediate
-    // offset (b65-68: EBT exceeds the histogram region, so the table starts
-    // later).  SPLIT: [OUTL | pad | X2 at T2 | X1 at TB | window rows]: S
-    // limbs (biased by EBT) are looked up at (TB - EBT) + S in X1 and at
-    // (T2 - EBT / 2) + S / 2 in X2, C limbs at TB + C and T2 + C / 2, all
-    // unsigned 16-bit immediate offsets.
-    static constexpr int T2 = SPLIT ? std::max((4 * NBINS + 15) / 16 * 16, ((int)EBT / 2 + 15) / 16 * 16) : 0;
-    static constexpr int TB0 = SPLIT ? (T2 + 4 * (int)B + 15) / 16 * 16 : (HIST_BYTES + 4 * NBINS + 15) / 16 * 16;
-    // VD & 32768 (small fields): no table image at all -- every limb decoded
-    // by VALU, limb 0 included -- so no per-workgroup table DMA (the table
-    // loads of a small field's hundreds of workgroups are fetched through the
-    // fabric: b40 1e6 spends a median 1.5 us, b80 1e6 4.6 us, of each
-    // workgroup's life on its state and tables; profiles/r06/stamps_r06.log)
-    static constexpr bool NOTAB = (VD_ & 32768) != 0;
-    static constexpr int TB = NOTAB || TB0 >= (int)EBT ? TB0 : ((int)EBT + 15) / 16 * 16;
-    static constexpr int OUTL = SPLIT ? 0 : HIST_BYTES;  // per-workgroup histogram of out-of-window counts
-    static constexpr int TC0 = (SPLIT ? T2 : TB) / 16 * 16;  // the table image starts here (16-byte copy)
-    // Low-digit entry, word 1: digit bits [0, DB), then the carries and flags
-    // of the step n -> n+1, all functions of n mod B (limb 0 of S, C, D1, N3
-    // is never stored): the carry out of S limb 0 of S += D1 and the carry
-    // (0..4) out of C limb 0 of C += 3S + N3; bit 30: D1 limb-0 wrap, bit 31:
-    // N3 limb-0 wrap (top bits, so "any flag" is one compare).  Up to b52 the
-    // carries sit pre-scaled by ES = 8 (a 4-bit field at F0 holding 8 * carry,
-    // a 6-bit field at FC holding 8 * carry: one v_bfe each gives the scaled
-    // carry); b53..58 leave room only for the bare carries (1 + 3 bits, one
-    // extra multiply-add per step); wider bases have no low-digit table.
-    static constexpr int DB = BASE - 32;
-    static constexpr bool TIGHT = DB > 20;
-    // VD & 16384 (small fields): no low-digit table, limb 0 stepped like the
-    // others (a 12.8 KB instead of a 38.4 KB table image at b40)
-    static constexpr bool LSD_W1 = MW == 2 && DB > 0 && DB + (TIGHT ? 4 : 10) <= 30 && (VD_ & (16384 | 32768)) == 0;
-    // VD & 1024 (probe A/B, b59..64: word 1 of the entry is all digit bits):
-    // the low-digit table with the carries and wrap flags in a side table of
-    // bytes (bit 0 the S carry, bits 1-3 the C carry, bit 6 / 7 the D1 / N3
-    // wraps), read at rc = TK + n mod B + i; r8 then holds TL too (TL can
-    // pass the 16-bit immediate offset).
-    static constexpr bool LSDX = MW == 2 && DB > 0 && !LSD_W1 && (VD_ & 1024) != 0;
-    static constexpr bool LSD = LSD_W1 || LSDX;
-    // (regions padded to 16 bytes: the image is copied in with 16-byte accesses)
-    static constexpr int TL = TB + (NOTAB ? 0 : ((int)(B * ES) + 15) / 16 * 16);  // low-digit table (LDE entries)
-    // Low-digit entries: a lane whose chunk starts at n reads n mod B + i, i <
-    // chunk <= B, so 2B cover any chunk.  The sibling kernels of b46+ keep
-    // B + 256 (their chunks are capped at 256, launch_sib): the table then
-    // leaves room for two 512-thread workgroups per CU.
-    static constexpr int LDE = (SIB_ > 1 && BASE_ >= 46) ? (int)B + 256 : 2 * (int)B;
-    static constexpr int TK = TL + (LSD ? ((int)(LDE * ES) + 15) / 16 * 16 : 0);  // LSDX: carry bytes
-    static constexpr int TEND = SPLIT ? (TB + (int)(B * ES) + 15) / 16 * 16
-                                      : TK + (LSDX ? ((int)(2 * B) + 15) / 16 * 16 : 0);
-    static constexpr int HB = SPLIT ? TEND : 0;  // window rows
-    // Sibling lanes: each sibling's cached C limbs [CL, NC) -- read and
-    // written only on the rare path -- as u16 per thread in LDS instead of
-    // VGPRs (slot (j, k) of thread t at COLD + 2 ((j NCOLD + k) WG + t)).
-    static constexpr int NCOLD = SIB_ > 1 ? NC - CL : 0;
-    static constexpr int COLD = TEND;
-    static constexpr int COLD_BYTES = (SIB_ * NCOLD * WG_ * 2 + 15) / 16 * 16;
-    static constexpr int LDS_BYTES = SPLIT ? HB + HIST_BYTES : TEND + COLD_BYTES;
-    static constexpr int TAB_BYTES = TEND - TC0;  // table image copied in per workgroup
-    static constexpr int ZA = SPLIT ? TC0 : TB;   // zeroed per workgroup: [0, ZA) and [HB, LDS_BYTES)
-    static constexpr int LO = LSD ? 1 : 0;  // first stored / looked-up limb
-    static constexpr u32 DMASK = (1u << (DB > 0 && DB < 32 ? DB : 0)) - 1;
-    static constexpr u32 FLAG_D1 = LSDX ? 1u << 6 : 1u << 30, FLAG_N3 = LSDX ? 1u << 7 : 1u << 31;  // any flag: w1 >= FLAG_D1
-    static constexpr int F0 = LSDX ? 0 : TIGHT ? DB : (DB + 3) / 4 * 4;
-    static constexpr int FC = LSDX ? 1 : TIGHT ? DB + 1 : F0 + 4;
-    static constexpr int F0W = TIGHT ? 1 : 4, FCW = TIGHT ? 3 : 6;  // field widths
-    // C += 3S + N3 (N3 = 3n + 1, NN limbs).  A C limb sum is < 5B, so its
-    // carry (0..4) is a multiply-high by MAGIC = ceil(2^32 / (ES B)) (exact
-    // over the range: static_assert).
-    static constexpr int NN = NX + 1;
-    static constexpr u32 DC = ES * B;
-    static constexpr u32 MAGIC = (u32)(((1ull << 32) + DC - 1) / DC);
-    static constexpr unsigned long long TMAX = (unsigned long long)ES * (5ull * B + 4);
-    // One multiply-high by MAGIC is exact because t is a multiple of ES:
-    // with t = ES u, u = qB + r and ES B MAGIC = 2^32 + e, the product is
-    // q + r / B + u e / (B 2^32), whose floor is q while u e < 2^32 (b80:
-    // u <= 5B + 4 = 32004, e = 98304).  Where even that fails, divide t / ES
-    // first.  (Rounds 1-3 bounded t e < 2^32 instead, which sent the
-    // 16-byte-entry bases b65..80 down the extra shift per C limb.)
-    static constexpr bool C1 = ((unsigned long long)MAGIC * DC - (1ull << 32)) * (TMAX / ES) < (1ull << 32);
-    static constexpr u32 MAGICB = (u32)(((1ull << 32) + B - 1) / B);
-    // VALU-decoded limbs (no table lookup): VD % 16 of the top stepped C
-    // limbs and VD / 16 of the top stepped S limbs.  Their two digits come
-    // from one multiply-high by MAGIC_D = ceil(2^32 / (ES b)) and set their
-    // bits with 64-bit shifts, trading VALU work (~6 ops at MW = 2, ~15 at
-    // MW = 3) for one data-random (bank-conflicting) LDS read.
-    static constexpr int VD = VD_;
-    static constexpr int VDC = VD % 16, VDS = (VD / 16) % 16;
-    // VD & 2048 (b65..80 probe): the VALU-decoded limbs sit just BELOW the
-    // top stepped limb instead of at it.  The top stepped limb only takes
-    // carries, so its value is nearly the same in every lane of a wave and
-    // its lookup is nearly a broadcast (4 LDS cycles on b80's index pattern),
-    // while the limbs below it cost 11-12 (scripts/ubench/lds_trace_gen.py).
-    static constexpr int VDB = (VD & 2048) ? 1 : 0;
-    // VD & 4096: the VALU-decoded limbs are the LOWEST ones above the
-    // low-digit table's limb (LO + 1 ...): the most data-random indices, whose
-    // lookups bank-conflict the most (sibling lanes, which have VALU to spare)
-    static constexpr bool VDLOW = (VD & 4096) != 0;
-    static constexpr bool vd_s(int q) {
-        if (NOTAB) return true;
-        return VDLOW ? (q > LO && q <= LO + VDS && q < SL) : (q >= SL - VDB - VDS && q < SL - VDB);
-    }
-    static constexpr bool vd_c(int q) {
-        if (NOTAB) return true;
-        return VDLOW ? (q > LO && q <= LO + VDC && q < CL) : (q >= CL - VDB - VDC && q < CL - VDB);
-    }
-    // Lookup groups: a scheduling barrier after every LG table lookups of a
-    // step (0: none), so the compiler cannot hoist all of a step's LDS reads
-    // ahead of their ORs -- with SPLIT's b64 + u16 pairs that held ~75 VGPRs
-    // of loaded words at once and spilled the 1024-thread b80 kernel at its
-    // 128-VGPR budget; the 16-byte layout spilled 52-64 bytes per lane there
-    // too, and LG 8 removes it (b80 1e9 7.45 -> 7.31 ms, lg_sweep.log).
-    // -1: the per-base default.
-    // (sibling lanes: LG >= 100 -- the default -- pipelines the siblings'
-    // lookups with the arithmetic, walk_sib_pipe; below 100 LG != 0 ends a
-    // group after each sibling's lookups, LG > 1 after every LG of them too)
-    static constexpr int LG = LG_ >= 0 ? LG_ : (SIB_ > 1 ? 100 : (MW == 3 && WG >= 1024 ? 8 : 0));
-    // Persistent grid: one round of resident workgroups, each walking a
-    // contiguous range of 64-unit batches that its waves pull from an LDS
-    // counter as they finish (instead of one chunk per lane and many rounds
-    // of workgroups, where a workgroup's CU idles down while its slowest
-    // wave finishes: b54 1e9, one 1024-thread workgroup per CU, waited 61 us
-    // of a 134 us workgroup life for it, profiles/r03/fd2_stamps_b54.log).
-    // -1: the per-base default.
-    // Sibling lanes: M = SIB numbers n0 + j B^2 per lane, in lock step.  n and
-    // n + j B^2 agree mod B^2, so limbs 0 and 1 of n^2, n^3, 2n + 1 and 3n + 1
-    // (radix B) are the same for all of them and so is the carry out of limb
-    // 1 of every chain: the low-digit lookup, limb 1's two lookups and limb 1's
-    // carry chains run once for the M numbers (walk_sib).  Rounds only.
-    static constexpr int SIB = SIB_;
-    static constexpr bool PERS = SIB_ > 1 ? false : PERS_ >= 0 ? PERS_ != 0 : (WG >= 1024 && one_wg_per_cu(BASE, WG));
-    // the same kernel with rounds of workgroups (launch_cfg falls back to it
-    // when the runtime occupancy or the field size does not suit PERS), at
-    // the workgroup size rounds prefer
-    using NoPers = Cfg<BASE_, ND_, NE_, NE2_, PROBE_, (PERS_ < 0 ? rounds_wg(BASE_) : WG_), VD_, LG_, 0>;
-    // the production kernel without sibling lanes (segments shorter than a
-    // few M B^2): the big-field workgroup size and VALU-decoded limbs; b46+
-    // keep the persistent-grid default of their regular kernel (b52..55 1e8
-    // fields: rounds of workgroups +8..+10 %, profiles/r05/sib_short_table_ab.log)
-    using NoSib = std::conditional_t<(BASE_ >= 46),
-                                     Cfg<BASE_, ND_, NE_, NE2_, PROBE_, big_wg(BASE_), valu_limbs_big(BASE_, ND_, NE_)>,
-                                     Cfg<BASE_, ND_, NE_, NE2_, PROBE_, rounds_wg(BASE_), valu_limbs_big(BASE_, ND_, NE_), -1, 0>>;
-    // lookup groups of walk_chunk (the sibling kernel's regular parts: none)
-    static constexpr int LGW = SIB_ > 1 ? 0 : (LG_ >= 0 ? LG_ : (MW == 3 && WG_ >= 1024 ? 8 : 0));
-    // VD & 256 (no low-digit table only): limb 0 of S and of C by VALU too --
-    // n^2 mod B and n^3 mod B of a wave's lanes keep few residues mod 16, so
-    // their lookups pile onto few bank quads
-    static constexpr bool VDL = ((VD & 256) != 0 || NOTAB) && !LSD;
-    static constexpr u32 MAGIC_D = (u32)(((1ull << 32) + ES * BASE - 1) / (ES * BASE));
-    static_assert(VD == 0 || (MW >= 2 && split_exact(BASE, ES, MAGIC_D)), "VALU digit split");
-    static_assert(VDC <= NE + 1 - (MW <= 2 ? 1 : 0) && VDS <= ND + 1 && (VD & ~0x1ffff) == 0 &&
-                      ((VD & 1024) == 0 || LSDX),
-                  "VALU-decoded limbs");
-    // Waves per SIMD: what the LDS allows, capped by what the lane state
-    // needs in VGPRs (the register budget is set to match, see state_waves).
-    static constexpr int WPE0 = (163840 / LDS_BYTES) * (WG / 64) / 4;
-    // (the small-field variants -- no low-digit table / no table -- at a
-    // 128-VGPR budget: a field below 1e7 puts only a few waves on each SIMD)
-    // (three mask words without a table: 256 VGPRs)
-    static constexpr int WREG = (VD_ & 32768) && MW == 3 ? 2 : (VD_ & (16384 | 32768)) ? 4 : sib_waves(BASE, SIB);
-    static constexpr int WPE1 = WPE0 < WREG ? WPE0 : WREG;
-    // in whole workgroups: k = the workgroups a CU holds at WPE1 waves per
-    // SIMD (a workgroup's WG / 64 waves spread over the 4 SIMDs), then the
-    // waves per SIMD those k workgroups need (640-thread workgroups: 2.5 each)
-    static constexpr int WGK = WPE1 * 256 / WG;
-    static constexpr int WPE = WGK > 0 ? (WGK * (WG / 64) + 3) / 4 : (WG / 64 + 3) / 4;
-    static_assert(WPE >= 1, "LDS: not even one workgroup fits");
-    static_assert(SL < NS && CL < NC && EL <= NE, "FD layout needs cached high limbs");
-    static_assert(ND <= NX + 1 && NE2 <= NX + 1 && NE <= NS + 1, "difference limb counts");
-    static_assert(S_TOPD >= 1 && C_TOPD >= 1, "top limb");
-    static_assert((NOTAB || TB >= (int)EBT) && (NOTAB || TB - (int)EBT < 65536) && (!LSD || LSDX || TL < 65536),
-                  "LDS offsets");
-    static_assert(!NOTAB || (!LSD && !SPLIT && SIB_ == 1), "table-free kernel: regular lanes, no low-digit table");
-    static_assert(!PERS || N64 || C64, "persistent grid: init() only (init_at is the rounds path's)");
-    static_assert(!SPLIT || (T2 >= (int)EBT / 2 && T2 < 65536 && T2 + 4 * (int)B <= TB && 4 * NBINS <= TC0 &&
-                             ES == 8 && TB < 65536),
-                  "split layout");
-    static_assert(LDS_BYTES <= 163840, "LDS");
-    static_assert(TB % 16 == 0 && TAB_BYTES % 16 == 0 && HB % 16 == 0, "16-byte table copy");
-    static_assert(W0 >= 0 && W0 + W <= NBINS, "window");
-    static_assert(!LSD || (ES == 8 && (LSDX ? TIGHT && FC + FCW <= 6 : FC + FCW <= 30)), "low-digit entry layout");
-    static_assert(C1 || ((unsigned long long)MAGICB * B - (1ull << 32)) * (TMAX / ES) < (1ull << 32),
-                  "C-limb carry magic");
-    static_assert(NN <= SL && NE >= NS, "C += 3S + N3 layout");
-    static_assert(3 * ES <= 64, "inline-constant multiplier");
-    static_assert(SIB == 1 || (LSD && MW == 2 && LO == 1 && SL >= 3 && CL >= 3 && ND >= 2 && NN >= 2),
-                  "sibling lanes share limb 1: low-digit-table bases only");
-    static_assert((unsigned long long)NX * B * B + 2ull * B < (1ull << 32), "32-bit init columns");
-};
-
 // v_mad_u32_u24 with an inline-constant multiplier (LLVM otherwise splits it
 // into v_mul_u32_u24 + v_add3_u32).
 template <u32 K>
@@ -1010,36 +558,6 @@ __global__ void fd2_tables_kernel(unsigned char *tb) {
     }
 }
 
-// The table image for this device and base, built on first use (the layout
-// depends on the base only) and kept for the process.
-template <class P>
-static hipError_t fd2_tables(hipStream_t s, const uint4 **out) {
-    if constexpr (P::TAB_BYTES == 0) {  // table-free kernel (Cfg::NOTAB)
-        (void)s;
-        *out = nullptr;
-        return hipSuccess;
-    }
-    static std::mutex mu;
-    static std::map<int, unsigned char *> have;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> g(mu);
-    auto it = have.find(dev);
-    if (it == have.end()) {
-        unsigned char *t = nullptr;
-        if ((e = hipMalloc(&t, P::TAB_BYTES)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(t, 0, P::TAB_BYTES, s)) != hipSuccess) return e;  // padding
-        hipLaunchKernelGGL(fd2_tables_kernel<P>, dim3((P::B + 255) / 256), dim3(256), 0, s, t);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        // other streams (contexts) of this device may read it next
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-        it = have.emplace(dev, t).first;
-    }
-    *out = (const uint4 *)it->second;
-    return hipSuccess;
-}
-
 // One launch covers a whole segment: blocks [0, main_blocks) walk `nunits`
 // chunks of `chunk` numbers from `start`; the blocks after them take the
 // < chunk numbers left over, one per lane, from `tail` (same code, chunk 1:
@@ -1050,7 +568,7 @@ static hipError_t fd2_tables(hipStream_t s, const uint4 **out) {
 // is ONE launch instead of main + tail + epilogue (under several fields in
 // flight each small launch waited for free CUs: 25-60 us apiece).
 // Probe build: per-workgroup phase stamps (scripts/fd2_stamps.py).  When
-// g_stamps (host, set by nice_probe_fd2_stamps) is non-null, thread 0 of each
+// g_stamps (host, fd2_launch.hpp, set by nice_probe_fd2_stamps) is non-null, thread 0 of each
 // workgroup b < kStampGroups writes kStampWords words at stamps + kStampWords b:
 // for each phase k the constant 100 MHz real-time counter (word 2k) and the
 // shader clock (word 2k + 1).  The stamps go only to that buffer; nothing
@@ -1058,9 +576,6 @@ static hipError_t fd2_tables(hipStream_t s, const uint4 **out) {
 // field finish.  (Product build: kProbes is false and Fd2Args::stamps null, so
 // a stamp compiles to nothing.)
 constexpr u32 kStampGroups = 65536, kStampWords = 32;
-NICE_PROBE_ONLY(extern u64 *g_stamps; extern u64 g_last_launch[6];)  // last launch: grid, WG, chunk, nunits, tail, per_cu
-// Forced sibling lane stride (nice_debug_force_sib_stride; 0: the model's pick).
-extern std::atomic<uint32_t> g_force_sib_stride;
 #define FD2_STAMP_P(p, k)                                                                        \
     do {                                                                                         \
         if (kProbes && (p) && threadIdx.x == 0 && blockIdx.x < kStampGroups) {                   \
@@ -1739,8 +1254,10 @@ __device__ __forceinline__ void walk_sib(State<P> (&st)[P::SIB], const unsigned 
 // its own text: with these two called from it instead, every fd2_kernel kept
 // its resource line but 6 369 instructions across the 131 instantiations came
 // out in another order (scripts/isa/kernel_diff.py), and the field kernels'
-// generated code is not to move for a feature they do not use.  Keep the two
-// in step with fd2_body.
+// generated code is not to move for a feature they do not use.  (Tried again
+// when the header was split four ways: the same 131 of 586 product kernels
+// differ, same instruction counts, another order.)  Keep the two in step with
+// fd2_body.
 //
 // A workgroup's start: the table image DMA'd into LDS and the histogram
 // region zeroed (see fd2_body).
@@ -1847,7 +1364,7 @@ __device__ __forceinline__ void fd2_body(const Fd2Args &a) {
     FD2_STAMP(a, 0);  // start
 
     // The tables (built once per device and base in global memory,
-    // fd2_tables) are DMA'd into LDS, and the histogram region zeroed:
+    // fd2_tables, fd2_launch.hpp) are DMA'd into LDS, and the histogram region zeroed:
     // building them here cost ~5 % of a launch of short chunks.  One
     // global_load_lds_dwordx4 wave-instruction moves 1 KiB (lane l's 16 bytes
     // land at the wave-uniform base + 16 l): every load of the copy is in
@@ -1868,7 +1385,7 @@ __device__ __forceinline__ void fd2_body(const Fd2Args &a) {
             for (u32 i = tid; i < (u32)(P::HIST_BYTES / 16); i += P::WG)
                 h4[P::HB / 16 + i] = make_uint4(0, 0, 0, 0);
     }
-    // A lane's first chunk (without PERS its only one: launch_cfg sizes the
+    // A lane's first chunk (without PERS its only one: plan_regular sizes the
     // grid to cover every unit) is set up while the table DMA is in flight;
     // only the cached high limbs' mask needs the tables.
     const u32 lane_id = tid & 63;
@@ -2057,18 +1574,6 @@ struct Fd2BatchArgs {
     const uint4 *tabs;
 };
 
-// The batch kernel's configuration for a (base, combo): what try_combo picks
-// for a small field, with rounds of workgroups.  LG_ and PERS_ are spelled out
-// at the values those kernels default to (two mask words or 512 threads: no
-// lookup groups), which makes the type -- and with it every device function
-// instantiated for it -- the batch kernel's own: sharing the instantiations
-// with fd2_kernel<P> of the same P moved that kernel's register allocation
-// by a VGPR or two (profiles/ranges/build_and_resources.txt).
-template <int B_, int ND_, int NE_, int NE2_>
-using BatchCfg = std::conditional_t<(valu_limbs(B_) & 1024) == 0,
-                                    Cfg<B_, ND_, NE_, NE2_, 0, 512, valu_limbs(B_), 0, 0>,
-                                    Cfg<B_, ND_, NE_, NE2_, 0, big_wg(B_), valu_limbs_big(B_, ND_, NE_), 0, 0>>;
-
 template <class P>
 __global__ void __launch_bounds__(P::WG) __attribute__((amdgpu_waves_per_eu(P::WPE, P::WPE)))
 fd2_batch_kernel(Fd2BatchArgs a) {
@@ -2109,501 +1614,6 @@ fd2_batch_kernel(Fd2BatchArgs a) {
     if (active) walk_chunk<P>(st, smem, chunk, n0_lo, n0_hi, hbase, hinc, outl, cutoff, out, probe_acc);
     __syncthreads();
     fd2_flush<P>(smem, a.hist, row, tid);  // row < 2^14 rows of a pass: row * kHistBins fits 32 bits
-}
-
-template <class P>
-static hipError_t launch_sib(const DetailedLaunch &p, int num_cus, hipStream_t s);
-
-// Radix-B digits of n, least significant first (Fd2Args::xs / xt).
-static inline void host_digits(u128 n, u32 B, u32 *out, int nx) {
-    for (int i = 0; i < nx; i++) {
-        out[i] = (u32)(n % B);
-        n /= B;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Lane stride from a bank-conflict model.  A wave's lanes sit `L` numbers
-// apart (one chunk each), so the value of a HIGH limb across the lanes is an
-// arithmetic progression whose step is f'(n) L / B^q (f = n^2, n^3).  A
-// table lookup costs, per pass of 32 lanes (8-byte entries) or 16 lanes
-// (16-byte entries), the largest number of distinct entries that share a
-// bank slot (entry mod 32 / mod 16): 1-2 for a progression with an odd step,
-// up to 32 for a step that is a multiple of 32 -- e.g. b40's top C limb
-// steps ~32 per lane at L = 125 from the range start (modelled 91 against
-// 63 LDS cycles per wave-step, measured 2.35 against 1.86 ms per 1e9 in the
-// sibling kernel), and L = 81 hits the same 10 % into the range (2.37 vs
-// 1.90 ms; profiles/r05/sib_chunk_sweep.log).  The low limbs' values are
-// effectively random whatever L is, so the model counts only the limbs
-// whose value f / B^q stays below 2^60 (long double keeps their integer
-// part), at a few points of the segment and of the chunk, and the launch
-// takes the candidate stride with the smallest modelled cost.
-// ---------------------------------------------------------------------------
-// Cost of one lookup pass (`slots` lanes on `slots` bank slots) whose lane
-// values are floor(a + d l) mod B, as a function of the step d at a
-// resolution of 1/64, averaged over the offset a: max distinct values per
-// slot.  The pattern of slots depends on d mod slots, but whether lanes
-// share a value (a broadcast, free) only on d itself, so the table covers
-// d in [0, 2 slots): steps >= slots are looked up at slots + d mod slots.
-// Simulated once per process.
-static const std::vector<float> &progression_cost(int slots) {
-    static std::mutex mu;
-    static std::map<int, std::vector<float>> tab;
-    std::lock_guard<std::mutex> g(mu);
-    auto it = tab.find(slots);
-    if (it != tab.end()) return it->second;
-    std::vector<float> t((size_t)slots * 128);
-    for (size_t k = 0; k < t.size(); k++) {
-        const double d = (double)k / 64;
-        double sum = 0;
-        for (int ai = 0; ai < 16; ai++) {
-            const double a = ai / 16.0 + 0.03125;
-            // the lane values floor(a + d l) never decrease with l, so a
-            // value repeats only in consecutive lanes (a broadcast)
-            int cnt[32] = {};
-            int best = 0;
-            long prev = -1;
-            for (int l = 0; l < slots; l++) {
-                const long v = (long)(a + d * l);  // a + d l >= 0: truncation is floor
-                if (v == prev) continue;
-                prev = v;
-                const int sl = (int)(v & (slots - 1));  // slots: 16 or 32
-                best = std::max(best, ++cnt[sl]);
-            }
-            sum += best;
-        }
-        t[k] = (float)(sum / 16);
-    }
-    return tab.emplace(slots, std::move(t)).first->second;
-}
-
-// Modelled LDS cycles of a wave-step's lookups of the limbs whose lane
-// values progress (the high looked-up limbs of S = n^2 and C = n^3 from
-// first_limb on, where the lanes' quadratic drift stays under half a unit)
-// at lane stride L, averaged over the segment's start, middle and end.  The
-// other limbs' values are effectively random whatever L is and are left out.
-// Per limb and point the lane step is c L and the drift k L^2 (c = f'(n) /
-// B^q, k = f''(n) 64^2 / 2 / B^q), so the strides of one pick share them.
-template <class P>
-struct ConflictModel {
-    static constexpr int SLOTS = P::ES == 16 ? 16 : 32;
-    static constexpr int NPASS = 64 / SLOTS;
-    int n = 0;
-    double c[3 * (P::SL + P::CL)], k[3 * (P::SL + P::CL)];
-    const std::vector<float> *tab;
-    ConflictModel(long double n0, long double span, int first_limb) : tab(&progression_cost(SLOTS)) {
-        for (int pt = 0; pt < 3; pt++) {
-            const long double x = n0 + span * (long double)pt / 2;
-            for (int cube = 0; cube < 2; cube++) {
-                const int hi = cube ? P::CL : P::SL;
-                long double bq = 1;
-                for (int q = 0; q < first_limb; q++) bq *= (long double)P::B;
-                for (int q = first_limb; q < hi; q++, bq *= (long double)P::B) {
-                    if (cube ? P::vd_c(q) : P::vd_s(q)) continue;
-                    const long double f1 = cube ? 3 * x * x : 2 * x;  // f'(n)
-                    const long double f2 = cube ? 6 * x : 2;          // f''(n)
-                    c[n] = (double)(f1 / bq);
-                    k[n] = (double)(f2 * 4096 / 2 / bq);
-                    n++;
-                }
-            }
-        }
-    }
-    double cost(u64 L) const {
-        double sum = 0;
-        const double l = (double)L;
-        for (int i = 0; i < n; i++) {
-            if (k[i] * l * l >= 0.5) continue;  // drifting: effectively random
-            // the lane step in limb units: < 2^24 for every limb that passes
-            // the drift test, so double keeps its fraction
-            const double d = c[i] * l;
-            const double r = d < SLOTS ? d : SLOTS + (d - SLOTS * std::floor(d / SLOTS));
-            sum += NPASS * (*tab)[std::min<size_t>(tab->size() - 1, (size_t)(r * 64))];
-        }
-        return sum / 3;
-    }
-};
-
-// The odd stride in [lo, hi] with the lowest modelled cost at the segment
-// [start, start + count); among the strides within `tol` modelled cycles of
-// the best, the one closest to target (a lane's init amortises over its
-// chunk).  A few hundred table lookups: cheap enough for every launch.
-// (A rounds-aware pick -- the stride whose units fill whole rounds of the
-// resident lanes, times L plus init steps -- chose L ~ 130-160 and lost on
-// small fields: b40 1e8 0.261 ms against 0.227 at L = 65, and did not gain at
-// 1e9; profiles/r05/picker_rounds.log.)
-template <class P>
-static u64 pick_lane_stride(u128 start, u64 count, u64 lo, u64 hi, u64 target, int first_limb,
-                            double tol = 0.5) {
-    const ConflictModel<P> m((long double)start, (long double)count, first_limb);
-    double cost[512];
-    int nc = 0;
-    double min_cost = 1e30;
-    for (u64 L = lo | 1; L <= hi && nc < 512; L += 2, nc++) {
-        cost[nc] = m.cost(L);
-        min_cost = std::min(min_cost, cost[nc]);
-    }
-    u64 best = target | 1, best_d = ~0ull;
-    nc = 0;
-    for (u64 L = lo | 1; L <= hi && nc < 512; L += 2, nc++) {
-        const u64 d = L > target ? L - target : target - L;
-        if (cost[nc] <= min_cost + tol && d < best_d) {
-            best = L;
-            best_d = d;
-        }
-    }
-    return best;
-}
-
-// The stride for fields of a few rounds (fewer than 3 at the target
-// stride): among the odd L in [lo, hi] the model does not flag, the one
-// whose units fill the fewest whole rounds of the resident lanes per step of
-// work, ceil(Q (ceil(D / L) - 1) / lanes) (L + init).  A part-filled last
-// round costs a whole one there: b40 1e8 (13 super-blocks) takes 0.227 ms at
-// L = 65 (1.95 rounds), 0.270 at L = 63 (2.01) and 0.259 at 61 (2.08); 9e7 is
-// best at 61 (1.76 rounds; profiles/r05/sib_small_L.log).  Sets `rounds`.
-template <class P>
-static u64 pick_small_stride(u128 start, u64 count, u64 lo, u64 hi, int first_limb, u64 Q, u64 lanes, u64 D,
-                             double &rounds, double init = 6, double tol = 6) {
-    const ConflictModel<P> m((long double)start, (long double)count, first_limb);
-    double cost[512];
-    int nc = 0;
-    double min_cost = 1e30;
-    for (u64 L = lo | 1; L <= hi && nc < 512; L += 2, nc++) {
-        cost[nc] = m.cost(L);
-        min_cost = std::min(min_cost, cost[nc]);
-    }
-    u64 best = lo | 1;
-    double best_t = 1e300;
-    rounds = 0;
-    nc = 0;
-    for (u64 L = lo | 1; L <= hi && nc < 512; L += 2, nc++) {
-        if (cost[nc] > min_cost + tol) continue;
-        const u64 units = Q * ((D + L - 1) / L - 1);
-        const double t = (double)((units + lanes - 1) / lanes) * ((double)L + init);
-        if (t < best_t) {
-            best_t = t;
-            best = L;
-            rounds = (double)units / (double)lanes;
-        }
-    }
-    return best;
-}
-
-template <class P>
-static hipError_t launch_cfg(const DetailedLaunch &p, int num_cus, hipStream_t s) {
-    if constexpr (P::SIB > 1) return launch_sib<P>(p, num_cus, s);
-    auto kern = fd2_kernel<P>;
-    // Occupancy is a property of the code object: queried once per
-    // instantiation (a runtime call per launch is host latency on small fields).
-    static const int per_cu_q = [&] {
-        int v = 0;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void *)kern, P::WG, 0) == hipSuccess
-                   ? v : -1;
-    }();
-    if (per_cu_q < 0) return hipErrorInvalidDeviceFunction;
-    const int per_cu = per_cu_q < 1 ? 1 : per_cu_q;
-    hipError_t e = hipSuccess;
-    // Resident lanes (one "round" of workgroups).
-    const u64 lanes = (u64)num_cus * per_cu * P::WG;
-    // Launch size bound (nunits fits 32 bits).  A lane takes ONE chunk per
-    // launch, so its window counters count at most chunk <= TCHUNK numbers
-    // (u16 halves; u8 quarters need chunk <= 255, checked below).
-    const u64 max_count = lanes * 60000ull;
-    // Every near-miss count must lie above the window (it is recorded on the
-    // out-of-window branch).
-    if (p.cutoff + 1 < (u32)(P::W0 + P::W)) return hipErrorInvalidValue;
-    // Target numbers per lane.  Short chunks put a wave's 64 lanes on nearby n,
-    // so the top stepped limbs (and the cached ones) of neighbouring lanes are
-    // equal or close and their lookups stop conflicting; a chunk still pays
-    // one init (radix-B conversion and products, ~10 steps).  Without PERS
-    // each lane takes one chunk and the grid is many rounds of workgroups:
-    // with two or more workgroups per CU, workgroups at different phases
-    // (table DMA, init, steps, draining) share a CU (b40 1e9 round 1: 2.49 ms
-    // persistent with static lane assignment at chunk 637, 2.31 at ~80,
-    // 2.19-2.21 in rounds, profiles/r01/fd2_chunk_sweep.log).
-    const u64 tchunk = probe_knob("NICE_FD2_TCHUNK", (u64)P::TCHUNK);
-    if constexpr (P::PERS) {
-        // The persistent grid pays off where ONE workgroup fills a CU and the
-        // segment needs at least two rounds of them; otherwise (a device with
-        // other occupancy, short segments) the same kernel in rounds.
-        if (per_cu_q != 1 || p.count < 2 * tchunk * lanes) return launch_cfg<typename P::NoPers>(p, num_cus, s);
-    }
-    const uint4 *tabs = nullptr;
-    if ((e = fd2_tables<P>(s, &tabs)) != hipSuccess) return e;
-    DetailedLaunch q = p;
-    u64 left = p.count;
-    while (left) {
-        u64 cnt = left < max_count ? left : max_count;
-        u64 chunk = 0, nunits = 0, tail = 0, grid = 0;
-        const u64 nw = P::WG / 64;
-        for (;;) {
-            // Chunk floor for fields too small to fill the chip: a lane's init
-            // costs about ten steps, but with idle CUs latency wins (b40 1e6:
-            // kernel 25 us at a floor of 32, 14 us at 4; scripts/small_fields.py).
-            const u64 min_chunk = probe_knob("NICE_FD2_MINCHUNK", 4);
-            // Whole rounds of workgroups, chunks <= the target (and <= B, the
-            // low-digit table's reach).
-            u64 rounds = (cnt + tchunk * lanes - 1) / (tchunk * lanes);
-            if (rounds < 1) rounds = 1;
-            chunk = (cnt + rounds * lanes - 1) / (rounds * lanes);
-            if (chunk < min_chunk) chunk = cnt < min_chunk ? cnt : min_chunk;
-            if (chunk < 1) chunk = 1;
-            // Odd chunks: lane l of a wave then sits at n mod B = r0 + chunk * l,
-            // so its low-digit entries fall on 32 distinct bank pairs per
-            // half-wave (B is a multiple of 32 for the LSD bases).  Without a
-            // low-digit table (b80) limb 0 of n^2 and n^3 is looked up in the
-            // pair table, and a chunk divisible by 16 puts a 16-lane group on
-            // ONE bank quad for those lookups (n^2 mod 16 equal on every lane):
-            // b80 1e9 at chunk 2544 took 11.8 ms, at 2545 9.3.
-            if (chunk > 1 && (P::LSD ? chunk % 2 == 0 : chunk % 16 == 0)) chunk++;
-            if (chunk > P::B) chunk = P::B % 2 ? P::B : P::B - 1;
-            // (The bank-conflict model that picks the sibling kernel's lane
-            // stride, pick_lane_stride, did not help the persistent-grid
-            // kernels of the wider bases: re-picking their chunk where it
-            // modelled a pathology moved b45..80 by -5 .. +9 %,
-            // profiles/r05/model_sweep.log, model_sweep2.log.)
-            if (P::HQ == 4 && chunk > 255) return hipErrorInvalidValue;
-            nunits = cnt / chunk;
-            tail = cnt - nunits * chunk;  // < chunk <= B: one number per lane
-            bool fits = nunits <= 0xffffffffull;
-            if constexpr (P::PERS) {
-                // one round of resident workgroups (fewer when the batches
-                // run out); the batch count stays in 32 bits and every
-                // workgroup's batches fit its waves' caps (u16 counters)
-                const u64 nb = (nunits + 63) / 64 + (tail + 63) / 64;
-                grid = std::min<u64>((u64)num_cus * per_cu, (nb + nw - 1) / nw);
-                fits = fits && nunits <= 0xffffffc0ull && (nb + grid - 1) / grid <= nw * (65535 / chunk);
-            } else {
-                grid = (nunits + P::WG - 1) / P::WG + (tail + P::WG - 1) / P::WG;
-            }
-            if (fits) break;
-            // Too much for one launch of this shape: split the segment (the
-            // finish rides on the last launch, so any split is exact).
-            if (cnt < 2) return hipErrorInvalidValue;
-            cnt /= 2;
-        }
-        const u64 main_blocks = (nunits + P::WG - 1) / P::WG;  // one chunk per lane
-        Fd2Args a{};
-        NICE_PROBE_ONLY(a.stamps = g_stamps;)
-        a.start_lo = q.start_lo;
-        a.start_hi = q.start_hi;
-        a.tail_lo = q.start_lo;
-        a.tail_hi = q.start_hi;
-        add_u128(a.tail_lo, a.tail_hi, nunits * chunk);
-        a.nunits = (u32)nunits;
-        a.chunk = (u32)chunk;
-        a.tail_count = (u32)tail;
-        a.main_blocks = (u32)main_blocks;
-        if constexpr (!P::N64 && !P::C64) {
-            host_digits(((u128)a.start_hi << 64) | a.start_lo, P::B, a.xs, P::NX);
-            host_digits(((u128)a.tail_hi << 64) | a.tail_lo, P::B, a.xt, P::NX);
-        }
-        a.cutoff = q.cutoff;
-        a.ncopies = q.hist_copies;
-        a.wave_cap = (u32)(65535 / chunk);
-        a.hist = q.hist;
-        a.out = q.out;
-        a.tabs = tabs;
-        // the field's finish rides on its last launch
-        a.fin = left == cnt ? q.fin : FieldFinish{nullptr, nullptr, 0, 0};
-        NICE_PROBE_ONLY({
-            const u64 v[6] = {grid, (u64)P::WG, chunk, nunits, tail, (u64)per_cu};
-            for (int k = 0; k < 6; k++) g_last_launch[k] = v[k];
-        })
-        hipLaunchKernelGGL(kern, dim3((u32)grid), dim3(P::WG), 0, s, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (p.launches) ++*p.launches;
-        add_u128(q.start_lo, q.start_hi, cnt);
-        left -= cnt;
-    }
-    return hipSuccess;
-}
-
-
-// One batch launch: `n` descriptors (all of this P's combo) from `units`.
-template <class P>
-static hipError_t launch_batch_cfg(const BatchLaunch &p, const Fd2Unit *units, u32 n, hipStream_t s) {
-    if (p.cutoff + 1 < (u32)(P::W0 + P::W)) return hipErrorInvalidValue;
-    const uint4 *tabs = nullptr;
-    hipError_t e = fd2_tables<P>(s, &tabs);
-    if (e != hipSuccess) return e;
-    Fd2BatchArgs a{};
-    a.units = units;
-    a.hist = p.hist;
-    a.ncopies = p.ncopies;
-    a.cutoff = p.cutoff;
-    a.out = p.out;
-    a.tabs = tabs;
-    hipLaunchKernelGGL(fd2_batch_kernel<P>, dim3(n), dim3(P::WG), 0, s, a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (p.launches) ++*p.launches;
-    return hipSuccess;
-}
-
-// Sibling-lane launches (Cfg::SIB = M > 1).  A segment [a, a + count) is
-// Q super-blocks of M B^2 numbers plus a remainder R < M B^2.  Super-block q
-// is walked by units (q, k): a lane takes the numbers a + q M B^2 + j B^2 +
-// k L + i (j < M, i < L) for k < B^2 / L, and the last L' = B^2 mod L (or L)
-// numbers of each B^2 block are the edge units (one per super-block, chunk
-// L'); the remainder R runs as the regular main + tail parts of the same
-// launch.  Launches are split so unit counts stay 32-bit; the field's finish
-// rides on the last.
-template <class P>
-static hipError_t launch_sib(const DetailedLaunch &p, int num_cus, hipStream_t s) {
-    auto kern = fd2_kernel<P>;
-    static const int per_cu_q = [&] {
-        int v = 0;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void *)kern, P::WG, 0) == hipSuccess
-                   ? v : -1;
-    }();
-    if (per_cu_q < 0) return hipErrorInvalidDeviceFunction;
-    const int per_cu = per_cu_q < 1 ? 1 : per_cu_q;
-    constexpr u64 D = (u64)P::B * P::B, SB = (u64)P::SIB * D;
-    const u64 lanes = (u64)num_cus * per_cu * P::WG;
-    // too short for the sibling walk to pay: the same base without siblings
-    if (p.count < 4 * SB) return launch_cfg<typename P::NoSib>(p, num_cus, s);
-    if (p.cutoff + 1 < (u32)(P::W0 + P::W)) return hipErrorInvalidValue;
-    const uint4 *tabs = nullptr;
-    hipError_t e = fd2_tables<P>(s, &tabs);
-    if (e != hipSuccess) return e;
-    // Sibling chunk L: odd, so limb 0's low-digit lookups of a half-wave hit
-    // 32 distinct bank pairs (as launch_cfg's chunks).
-    const u128 seg_start = ((u128)p.start_hi << 64) | p.start_lo;
-    u64 L = probe_knob("NICE_FD2_SIBCHUNK", 0);
-    // a stride forced by the test hook also skips the small-field fallback
-    // below (every stride the pickers can return is then reachable on a
-    // field of >= 4 super-blocks)
-    if (!L) L = g_force_sib_stride.load(std::memory_order_relaxed);
-    // Fields of fewer than 6 rounds of the resident lanes' units at the
-    // target stride: the part-filled last round of the 4-wave grid decides,
-    // so the stride fills rounds (pick_small_stride over [60, 100]), and
-    // below ~1.5 rounds the regular kernel's finer grid wins (b40 1e8:
-    // sibling 0.227-0.239 ms at L = 65 against 0.242-0.265 regular, 1.25e8
-    // 0.263-0.289 against 0.282-0.307; 9e7 ties; profiles/r05/
-    // sib_small_L.log; the 4- and 8-way shards of the bench field,
-    // shard_projection.log).
-    // A field that overlaps a running one (pipelined submits) shares the chip
-    // with it, so no round is part-filled and the per-number cost decides:
-    // the large-field pick.  The 8-way shard of the bench field (1.25e8),
-    // pipelined: 0.2412 ms per step at L = 105, 0.2422 at 81, 0.2481 at the
-    // small-field pick (79 / 81 / 65 by shard); 2.5e8 0.486 / 0.494 / 0.500,
-    // 5e7 0.110 / 0.113 / 0.112, 1e8 0.1940 / 0.1938 / 0.1952, and L = 125
-    // 20-25 % slower everywhere (profiles/r06/exchange/small_L_pipe.log).
-    const u64 Q0 = p.count / SB;
-    if (!L && !p.overlapped && 10 * Q0 * (D / P::TCHUNK) < 60 * lanes) {
-        double rounds = 0;
-        L = pick_small_stride<P>(seg_start, p.count, P::TCHUNK * 3 / 4, P::TCHUNK * 5 / 4, P::LO + 1, Q0, lanes, D,
-                                 rounds);
-        if (10 * rounds < (double)probe_knob("NICE_FD2_SIBROUNDS", 15))
-            return launch_cfg<typename P::NoSib>(p, num_cus, s);
-    }
-    // Target stride: TCHUNK, or 140 for the pipelined walk (LG >= 100), which
-    // fills and drains its lookup pipeline once per unit and so gains from
-    // longer units.  b40 bench field (pipelined, stride swept over odd L in
-    // [61, 255] against the pick, profiles/r06/stride/): target 80 picked
-    // 65 at 1e9 (1.917 ms per field), target 140 picks 143 (-2.5 %) there and
-    // 159 at 1.25e8 (-2.7 %); a quarter into the range -0.6 / -2.8 %.  The
-    // per-sibling-lookup kernels (LG 1, b40 beyond the first limb layout and
-    // b42..55) gain nothing consistent from longer targets (b42 1.25e8 +14 %
-    // at 140), so they keep TCHUNK.
-    constexpr u64 T = P::LG >= 100 ? 140 : (u64)P::TCHUNK;
-    // A lone field of the pipelined walk (a synchronous caller, the reference
-    // client's pattern: nothing overlaps its last round) picks over the same
-    // range by whole rounds, as the small-field path does: b40 1e9 alone
-    // 1875-1887 us at L = 159 (7.99 rounds) against 1890-1947 at the model's
-    // 143 (8.9 rounds), 5e8 953 against 973-1012 (profiles/r06/stride/
-    // iso_L.log).  Pipelined fields keep the model's pick (no last round).
-    if (!L && P::LG >= 100 && !p.overlapped) {
-        double rounds = 0;
-        L = pick_small_stride<P>(seg_start, p.count, T * 3 / 4, T * 3 / 2, P::LO + 1, Q0, lanes, D, rounds);
-    }
-    if (!L) L = pick_lane_stride<P>(seg_start, p.count, T * 3 / 4, T * 3 / 2, T, P::LO + 1);
-    // chunks reach low-digit entries n mod B + i < LDE (Cfg::LDE)
-    constexpr u64 LMAX = (u64)P::LDE - P::B;
-    if (L % 2 == 0) L++;
-    if (L > D / 4) L = (D / 4) | 1;
-    if (L > LMAX) L = LMAX % 2 ? LMAX : LMAX - 1;
-    const u64 U = (D + L - 1) / L, r = D - (U - 1) * L;
-    const bool has_edge = r != L;
-    const u64 upb = has_edge ? U - 1 : U;
-    // the lanes' u16 window counters hold M L numbers
-    if ((u64)P::SIB * L > 65535) return hipErrorInvalidValue;
-    if (p.sib) {
-        p.sib[0] = (uint32_t)P::SIB;
-        p.sib[1] = (uint32_t)L;
-    }
-    // Launch bound: unit counts in 32 bits and, as launch_cfg's, 60 000
-    // numbers per resident lane -- counted at the regular kernel's 2048 lanes
-    // per CU, so a b40 launch still takes up to 3.1e10 numbers whatever the
-    // sibling kernel's own occupancy.
-    const u64 qmax = std::max<u64>(1, std::min<u64>(0xffffffffull / upb, ((u64)num_cus * 2048 * 60000ull) / SB));
-    DetailedLaunch q = p;
-    u64 left = p.count;
-    const u64 tchunk = probe_knob("NICE_FD2_TCHUNK", (u64)P::TCHUNK);
-    while (left) {
-        u64 Q = left / SB, cnt = left;
-        if (Q > qmax) {
-            Q = qmax;
-            cnt = Q * SB;
-        }
-        // regular remainder (the last launch only): rounds of one chunk per lane
-        const u64 R = cnt - Q * SB;
-        u64 chunk = 1, nunits = 0, tail = 0;
-        if (R) {
-            u64 rounds = (R + tchunk * lanes - 1) / (tchunk * lanes);
-            if (rounds < 1) rounds = 1;
-            chunk = (R + rounds * lanes - 1) / (rounds * lanes);
-            if (chunk < 4) chunk = R < 4 ? R : 4;
-            if (chunk < 1) chunk = 1;
-            if (chunk > 1 && chunk % 2 == 0) chunk++;
-            if (chunk > LMAX) chunk = LMAX % 2 ? LMAX : LMAX - 1;
-            nunits = R / chunk;
-            tail = R - nunits * chunk;
-        }
-        Fd2Args a{};
-        NICE_PROBE_ONLY(a.stamps = g_stamps;)
-        a.sib_lo = q.start_lo;
-        a.sib_hi = q.start_hi;
-        a.sib_chunk = (u32)L;
-        a.sib_upb = (u32)upb;
-        a.sib_units = (u32)(Q * upb);
-        a.sib_blocks = (u32)((Q * upb + P::WG - 1) / P::WG);
-        a.edge_lo = q.start_lo;
-        a.edge_hi = q.start_hi;
-        add_u128(a.edge_lo, a.edge_hi, upb * L);
-        a.edge_chunk = (u32)r;
-        a.edge_units = has_edge ? (u32)Q : 0u;
-        a.edge_blocks = has_edge ? (u32)((Q + P::WG - 1) / P::WG) : 0u;
-        a.start_lo = q.start_lo;
-        a.start_hi = q.start_hi;
-        add_u128(a.start_lo, a.start_hi, Q * SB);
-        a.tail_lo = a.start_lo;
-        a.tail_hi = a.start_hi;
-        add_u128(a.tail_lo, a.tail_hi, nunits * chunk);
-        a.nunits = (u32)nunits;
-        a.chunk = (u32)chunk;
-        a.tail_count = (u32)tail;
-        a.main_blocks = (u32)((nunits + P::WG - 1) / P::WG);
-        a.cutoff = q.cutoff;
-        a.ncopies = q.hist_copies;
-        a.wave_cap = 0;
-        a.hist = q.hist;
-        a.out = q.out;
-        a.tabs = tabs;
-        a.fin = left == cnt ? q.fin : FieldFinish{nullptr, nullptr, 0, 0};
-        const u64 grid = (u64)a.sib_blocks + a.edge_blocks + a.main_blocks + (tail + P::WG - 1) / P::WG;
-        NICE_PROBE_ONLY({
-            const u64 v[6] = {grid, (u64)P::WG, L, Q * upb, R, (u64)per_cu};
-            for (int k = 0; k < 6; k++) g_last_launch[k] = v[k];
-        })
-        hipLaunchKernelGGL(kern, dim3((u32)grid), dim3(P::WG), 0, s, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (p.launches) ++*p.launches;
-        add_u128(q.start_lo, q.start_hi, cnt);
-        left -= cnt;
-    }
-    return hipSuccess;
 }
 
 }  // namespace fd2

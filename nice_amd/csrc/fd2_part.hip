@@ -3,7 +3,7 @@
 // bases with fd2_part_of(base) == k, so the ~70 kernel instantiations of
 // FD2_COMBOS compile in parallel.
 #include "fd2_combos.h"
-#include "fd2_kernel.hpp"
+#include "fd2_launch.hpp"
 
 #ifndef FD2_PART
 #error "build with -DFD2_PART=k"
@@ -29,7 +29,7 @@ static hipError_t try_combo(const DetailedLaunch &p, int nd, int ne, int ne2, bo
                       "lds_bytes mirrors Cfg");
 #include NICE_PROBE_INC("fd2_part_probe_dispatch.inc")
         // b40 fields >= 1e7: three sibling lanes (Cfg::SIB, fd2_kernel.hpp;
-        // launch_sib falls back to the regular kernel below ~1.5 rounds of
+        // plan_sib falls back to the regular kernel below ~1.5 rounds of
         // sibling units): on the first limb layout (the range's first ~29 %,
         // the benchmark fields) pipelined with the lowest C limb above the
         // shared one decoded by VALU, elsewhere per-sibling lookup groups, no

@@ -77,7 +77,7 @@ uint32_t fd2_batch_chunk(uint32_t base);
 // The units of [start, end) (inside the base's valid range): cut at the limb
 // layout changes, each piece tiled into main workgroups (one chunk per lane)
 // plus at most one tail workgroup (the < chunk numbers left over, one per
-// lane).  Appended to `out` in ascending n.  Pure host code.
+// lane).  Appended to `out` in ascending n.  Pure host code (the tiling of a piece: fd2_plan.hpp batch_tile).
 void fd2_batch_plan(uint32_t base, unsigned __int128 start, unsigned __int128 end, uint32_t row,
                     std::vector<BatchUnit> &out);
 struct BatchLaunch {
@@ -95,9 +95,9 @@ struct BatchLaunch {
 // enqueues one launch per combo present.
 hipError_t launch_detailed_fd2_batch(const BatchLaunch &p, hipStream_t s);
 // Test hook: every later sibling-lane launch of the process uses lane stride
-// L (odd; 0 restores the production pick, fd2_kernel.hpp launch_sib).
+// L (odd; 0 restores the production pick, fd2_plan.hpp plan_sib).
 void fd2_force_sib_stride(uint32_t L);
-// The base's compile-time histogram window [w0, w0 + w) (fd2_kernel.hpp
+// The base's compile-time histogram window [w0, w0 + w) (fd2_cfg.hpp
 // window_w0 / window_w); false for a base without an FD kernel.  The FD
 // launchers accept a cutoff with cutoff + 1 >= w0 + w.
 bool fd2_window(uint32_t base, uint32_t *w0, uint32_t *w);

@@ -8,6 +8,12 @@
 
 namespace nice {
 
+typedef uint32_t u32;
+typedef uint64_t u64;
+typedef unsigned __int128 u128;
+
+constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
+
 // Detailed histograms: rows of kHistBins u64 bins (bin u = numbers with u
 // unique digits, u <= 128).  A field's state block holds kHistCopies rows
 // (summed at its end); a workgroup flushes into copy blockIdx.x % kHistCopies.

@@ -17,11 +17,6 @@
 
 namespace nice {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
-
-constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
-
 // --------------------------------------------------------------------------
 // Digit masks: MW words of 32 bits (base <= 32 -> 1, <= 64 -> 2, <= 128 -> 4).
 // --------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""Histogram windows of the FD kernel per base (fd2_kernel.hpp Cfg::W0/W):
+"""Histogram windows of the FD kernel per base (fd2_cfg.hpp Cfg::W0/W):
 the unique-count distribution of in-range n sampled uniformly (the oracle's
 num_unique_digits), and for a window width W the start W0 that covers the
 most mass with W0 + W <= cutoff + 1 (every near-miss must fall outside the

@@ -1,4 +1,4 @@
-// Host-only dump of launch_sib's stride model (fd2_kernel.hpp) for the
+// Host-only dump of plan_sib's stride model (fd2_plan.hpp) for the
 // sibling-lane configurations: ConflictModel cost of every odd L in [lo, hi]
 // at a segment [start, start + count), and pick_lane_stride's choice for a
 // few targets.  No GPU call is made.
@@ -8,10 +8,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include "../../nice_amd/csrc/fd2_kernel.hpp"
+#include "../../nice_amd/csrc/fd2_cfg.hpp"
+#include "../../nice_amd/csrc/fd2_plan.hpp"
 using namespace nice;
 using namespace nice::fd2;
-std::atomic<uint32_t> nice::fd2::g_force_sib_stride{0};  // (defined by fd2_detailed.hip in the library)
 
 static u128 parse_u128(const char *s) {
     u128 v = 0;
@@ -27,7 +27,7 @@ static int dump(u128 start, u64 count, int lo, int hi) {
     for (u64 t : {80ull, 100ull, 140ull, 160ull, 240ull})
         printf("pick_lane_stride target %llu: %llu\n", (unsigned long long)t,
                (unsigned long long)pick_lane_stride<P>(start, count, t * 3 / 4, t * 3 / 2, t, P::LO + 1));
-    // the lone-field rounds pick (launch_sib, LG >= 100) at 2 x 512-thread
+    // the lone-field rounds pick (plan_sib, LG >= 100) at 2 x 512-thread
     // workgroups per CU on 256 CUs
     if constexpr (P::SIB > 1) {
         constexpr u64 D = (u64)P::B * P::B, SB = (u64)P::SIB * D;

@@ -9,7 +9,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "../../nice_amd/csrc/fd2_kernel.hpp"
+#include "../../nice_amd/csrc/fd2_launch.hpp"
 
 using namespace nice;
 using namespace nice::fd2;

@@ -1,5 +1,5 @@
 """Host-side checks of the FD kernel's carry arithmetic (nice_amd/csrc/
-fd2_kernel.hpp, Cfg::C1): the carry (0..4) out of a C limb sum t < ES (5B + 4)
+fd2_cfg.hpp, Cfg::C1): the carry (0..4) out of a C limb sum t < ES (5B + 4)
 is ONE multiply-high by MAGIC = ceil(2^32 / (ES B)), because t is always a
 multiple of the table entry size ES.  Checked exhaustively over every
 multiple of ES for every base with an FD instantiation (no GPU needed)."""

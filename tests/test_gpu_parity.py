@@ -466,7 +466,7 @@ def test_persistent_grid_equals_rounds(ctx, base):
 
 @pytest.mark.parametrize("base,size", [(40, 32 * 10 ** 9), (80, 16 * 10 ** 9)])
 def test_detailed_field_longer_than_one_launch(ctx, base, size):
-    """launch_cfg (fd2_kernel.hpp) splits a segment into launches of at most
+    """plan_regular (fd2_plan.hpp) splits a segment into launches of at most
     60 000 numbers per resident lane: 3.1e10 at b40 (two 1024-thread
     workgroups per CU), 1.6e10 at b80 (one, persistent grid); the field's
     finish rides on its last launch.  The reference batches any field size
@@ -489,7 +489,7 @@ def test_detailed_field_longer_than_one_launch(ctx, base, size):
 
 
 # Where the per-layout VALU-decode choice of fields >= 1e7 (valu_limbs_big,
-# fd2_kernel.hpp) changes the kernel: b40 on its 8-limb n^3 layouts and
+# fd2_cfg.hpp) changes the kernel: b40 on its 8-limb n^3 layouts and
 # b50/53/60 (below-top decode), b65/67/68
 # (limb 0 + two / three below the top), b80 on its 16-limb layouts (the first
 # ~40 % of the range) and on the 17-limb one (four below the top).
@@ -1306,8 +1306,8 @@ def test_eight_shard_context():
                                        (53, 0.5), (54, 0.6), (55, 0.0), (55, 0.8)])
 def test_sibling_kernel_equals_small_fields(ctx, base, frac):
     """b40 fields of >= ~1e8 numbers (1.5 rounds of the resident lanes'
-    units, launch_sib's NICE_FD2_SIBROUNDS default 15 / 10) run the
-    sibling-lane kernel (Cfg::SIB = 3, fd2_kernel.hpp: a
+    units, plan_sib's NICE_FD2_SIBROUNDS default 15 / 10) run the
+    sibling-lane kernel (Cfg::SIB = 3, fd2_cfg.hpp: a
     lane steps n, n + B^2 and n + 2 B^2 together, sharing limbs 0 and 1;
     super-blocks, edge units where the lane stride does not divide B^2, and
     the regular remainder in one launch; the lane stride from the
@@ -1373,7 +1373,7 @@ def test_every_sibling_lane_stride(ctx, base, frac, strides):
     """the sibling kernels pick their lane stride L per
     launch (pick_lane_stride over odd L in [0.75, 1.5] T -- T = 140 for the
     pipelined walk, else TCHUNK: 80 at b40, 160 at b52 -- pick_small_stride
-    over [0.75, 1.25] TCHUNK, fd2_kernel.hpp), and every L that does not divide
+    over [0.75, 1.25] TCHUNK, fd2_plan.hpp), and every L that does not divide
     B^2 leaves an edge unit per super-block.  With the stride forced through
     nice_debug_force_sib_stride, each odd L of those ranges ([45, 210] on the
     b40 bench layout, M = 3; [45, 240] on b52, M = 2; a sample on b40's other
