@@ -219,7 +219,7 @@ int run_device_msd(nice_ctx *ctx, int t, NiceJob &job, const NiceField &f, nice_
         Device &d = ctx->devs[i];
         Slot &sl = d.slot[t];
         HIPCHK(hipSetDevice(d.id));
-        const uint64_t fgrid = std::min<uint64_t>(pl.cpb, (uint64_t)d.num_cus * 4);
+        const uint64_t fgrid = nice::msd_fused_grid(pl.cpb, d.num_cus);
         int r = pl.fcap   ? ensure_msd(sl, 0, (uint32_t)pl.leaf_cap, fgrid * 2 * pl.fcap, 0, prefix)
                 : pl.wave ? ensure_msd(sl, (uint32_t)pl.per, (uint32_t)pl.wleaf_cap, 0,
                                        nice::msd_wave_scratch_bytes(pl.wgrid), prefix)
@@ -289,7 +289,7 @@ int run_device_msd(nice_ctx *ctx, int t, NiceJob &job, const NiceField &f, nice_
             st.launches++;
             continue;
         }
-        const uint32_t fgrid = (uint32_t)std::min<uint64_t>(mp.nchunks, (uint64_t)d.num_cus * 4);
+        const uint32_t fgrid = (uint32_t)nice::msd_fused_grid(mp.nchunks, d.num_cus);
         hipError_t err = pl.fcap ? nice::launch_msd_device(mp, d.num_cus, sl.nstream, mb.scratch, pl.fcap, fgrid, snd)
                                  : nice::launch_msd_device(mp, d.num_cus, sl.nstream, nullptr, 0, 0, snd);
         if (err != hipSuccess) return fail(NICE_ERR_HIP, std::string("msd launch: ") + hipGetErrorString(err));

@@ -1,5 +1,6 @@
 // kernels.h -- host-side launch entry points for the gfx950 kernels
-// (implemented in detailed.hip / niceonly.hip / niceonly_part.hip, used by
+// (implemented in detailed.hip / niceonly.hip / niceonly_part.hip -- the
+// niceonly kernel templates: niceonly_cand.hpp and the headers it lists -- used by
 // the C ABI files, abi_*.cpp).  The word layouts host and device share are in
 // layout.h.
 #pragma once
@@ -210,13 +211,9 @@ struct MsdLaunch {
 struct ChunkNode {
     uint32_t off, size;
 };
-constexpr uint32_t kFusedMaxCap = 1u << 14;
-// Nodes per level of a fused chunk recursion (a power of two), or 0 when the
-// chunk needs the level-launch BFS (chunk / floor too large, or chunk >= 2^32).
-uint32_t msd_fused_cap(uint64_t chunk, uint64_t floor_size);
 // Enqueue a batch's MSD recursion (no host sync): with `scratch` (grid x 2 x
-// cap ChunkNodes) ONE fused launch, one workgroup per chunk; otherwise the
-// init + level kernels.
+// cap ChunkNodes; msd_plan.hpp msd_fused_cap, msd_fused_grid) ONE fused
+// launch, one workgroup per chunk; otherwise the init + level kernels.
 hipError_t launch_msd_device(const MsdLaunch &p, int num_cus, hipStream_t s, ChunkNode *scratch = nullptr,
                              uint32_t cap = 0, uint32_t grid = 0, const SoundLaunch *snd = nullptr);
 
@@ -225,12 +222,10 @@ hipError_t launch_msd_device(const MsdLaunch &p, int num_cus, hipStream_t s, Chu
 // level0 AND the candidate test of every leaf in one launch (`c` holds the
 // residues, output and finish; its leaf fields are unused), `grid` workgroups
 // of msd_wave_waves_per_group() waves, each wave with a kStackCap-node stack
-// in `scratch` (msd_wave_scratch_bytes(grid)).  Leaves of the BFS levels go
-// to p.leaves and are tested by the same launch.
+// in `scratch` (msd_wave_scratch_bytes(grid); both msd_plan.hpp).  Leaves of
+// the BFS levels go to p.leaves and are tested by the same launch.
 hipError_t launch_msd_wave(const MsdLaunch &p, const NiceonlyLaunch &c, uint32_t level0, void *scratch,
                            uint32_t grid, int num_cus, hipStream_t s, const SoundLaunch *snd = nullptr);
-size_t msd_wave_scratch_bytes(uint32_t grid);
-uint32_t msd_wave_waves_per_group();
 
 // Diagnostics used by the parity tests: per-n unique counts / nice flags
 // computed by the same device functions the production kernels use.

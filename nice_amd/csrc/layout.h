@@ -62,6 +62,19 @@ constexpr uint32_t kMsdMappedWords = 34;
 // several leaves, so niceonly_kernel's per-wave sums of 8 leaves fit 32 bits.
 constexpr uint32_t kLeafPiece = 1u << 28;
 
+// msd_fused_kernel: the most nodes a level of a chunk's recursion may hold
+// (msd_plan.hpp msd_fused_cap).
+constexpr uint32_t kFusedMaxCap = 1u << 14;
+
+// msd_wave_kernel (niceonly_wave.hpp): threads per workgroup -- the pair table
+// (<= 23 KB) is shared by 8 waves, two workgroups per CU at 4 waves per SIMD.
+constexpr uint32_t kWaveWG = 512;
+// Its work stack per wave: a pop takes <= 64 nodes off the top and pushes <= 128
+// one level deeper, so at most ~64 nodes per level stay behind (23 levels) plus
+// one refill of 64 roots; overflow sets the MSD overflow flag (an error).
+constexpr uint32_t kStackCap = 2048;
+constexpr uint32_t kStackNodeBytes = 16;  // sizeof(StackNode)
+
 static_assert(kFinCount == kHistBins && kFinSeq > kFinCount && kFinWords > kFinSeq, "result words follow the bins");
 static_assert(kMsdLeafCount == kMsdLevels && kMsdSquareOk < kMsdCandidates, "u32 counters follow the level sizes");
 static_assert(kMsdCandidates % 2 == 0 && kMsdNumbers % 2 == 0 && kMsdRejected % 2 == 0 &&

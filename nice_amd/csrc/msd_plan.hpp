@@ -1,8 +1,9 @@
-// msd_plan.hpp -- how a niceonly field's device MSD is cut into batches and
-// how large its buffers are: pure arithmetic (no HIP), so it can be checked
-// on its own.
+// msd_plan.hpp -- how a niceonly field's device MSD is cut into batches, how
+// large its buffers are and how many workgroups each of its launches gets:
+// pure arithmetic (no HIP), checked on its own by tests/test_msd_plan.py.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -10,6 +11,60 @@
 #include "layout.h"
 
 namespace nice {
+
+// Nodes per level of a fused chunk recursion (msd_fused_kernel; a power of
+// two), or 0 when the chunk needs the level-launch BFS (chunk / floor too
+// large, or chunk >= 2^32).
+inline uint32_t msd_fused_cap(uint64_t chunk, uint64_t floor_size) {
+    if (chunk > 0xffffffffull || floor_size == 0) return 0;
+    const uint64_t need = chunk / floor_size + 2;
+    if (need > kFusedMaxCap) return 0;
+    uint32_t cap = 64;
+    while (cap < need) cap <<= 1;
+    return cap;
+}
+// ... and its workgroups: one per chunk of the batch (grid-strided past 4 per CU).
+inline uint64_t msd_fused_grid(uint64_t chunks, int num_cus) { return std::min<uint64_t>(chunks, (uint64_t)num_cus * 4); }
+
+// msd_wave_kernel: waves per workgroup, and the work stacks of `grid` workgroups.
+inline uint32_t msd_wave_waves_per_group() { return kWaveWG / 64; }
+inline size_t msd_wave_scratch_bytes(uint32_t grid) {
+    return (size_t)grid * msd_wave_waves_per_group() * kStackCap * kStackNodeBytes;
+}
+
+// The last level of the level BFS that can hold a node that splits.  A node
+// of level d has at most ceil(chunk / 2^d) numbers and splits only if it
+// holds >= 2 * floor, so levels past the first d with ceil(chunk / 2^d) <
+// 2 * floor are empty (b40 1e9 field, chunk 1e6, floor 250: levels 0..11
+// instead of 0..22).
+inline uint32_t msd_last_level(uint64_t chunk, uint64_t floor_size) {
+    uint32_t last = 0;
+    while (last < 22 && ((chunk + (1ull << last) - 1) >> last) >= 2 * floor_size) last++;
+    return last;
+}
+
+// Workgroups (256 lanes, one per node) of msd_level_kernel at `level`: the
+// level holds <= nchunks * 2^level nodes (the first levels are a few thousand
+// lanes), capped at 2 per CU -- also when that product overflows.
+inline uint32_t msd_level_grid(uint64_t nchunks, uint32_t level, int num_cus) {
+    const uint64_t nodes = level < 40 ? nchunks << level : ~0ull;
+    uint64_t grid = (nodes + 255) / 256;
+    const uint64_t cap = (uint64_t)num_cus * 2;
+    if (grid > cap || nodes >> level != nchunks) grid = cap;
+    return (uint32_t)grid;
+}
+
+// Workgroups (4 waves) of niceonly_kernel: a wave per 8 leaves, or 32 waves
+// per CU when the leaf count is on the device; at most `cap` (8 per CU; the
+// probe build's NICE_NICE_GRID), at least 1.
+inline uint32_t nice_grid(bool count_on_device, uint32_t n_leaves, int num_cus, uint64_t cap) {
+    const uint64_t waves = count_on_device ? (uint64_t)num_cus * 32 : ((uint64_t)n_leaves + 7) / 8;
+    uint64_t grid = (waves + 3) / 4;
+    if (grid > cap) grid = cap;
+    if (grid < 1) grid = 1;
+    return (uint32_t)grid;
+}
+
 namespace abi __attribute__((visibility("hidden"))) {
 
 struct MsdPlan {
@@ -40,7 +95,8 @@ inline uint64_t nbatches_of(uint64_t chunks, uint64_t per_batch) { return (chunk
 
 // chunk, floor_size: the field's MSD chunk size and recursion floor; mine: the
 // caller's chunks (> 0); max_cus: the largest device; fused_cap:
-// msd_fused_cap(chunk, floor_size); waves_per_group: msd_wave_waves_per_group().
+// msd_fused_cap(chunk, floor_size), or the probe build's override;
+// waves_per_group: msd_wave_waves_per_group().
 inline MsdPlan plan_device_msd(unsigned __int128 chunk, uint64_t floor_size, uint64_t mine, size_t n_devices,
                                int max_cus, uint32_t fused_cap, uint32_t waves_per_group,
                                const MsdPlanKnobs &knobs = MsdPlanKnobs{}) {
@@ -84,8 +140,7 @@ inline MsdPlan plan_device_msd(unsigned __int128 chunk, uint64_t floor_size, uin
         // at 2048; a 1/8 dealt share 0.0135 / 0.0101 s, scripts/roots_sweep.py)
         const uint64_t waves = (uint64_t)pl.wgrid * waves_per_group;
         const uint64_t target = waves * knobs.roots;
-        uint32_t last = 0;  // first level without splits
-        while (last < 22 && ((cnk + (1ull << last) - 1) >> last) >= 2 * fl) last++;
+        const uint32_t last = msd_last_level(cnk, fl);
         uint32_t wlevel = 0;
         while (wlevel < last && ((cnk + (1ull << wlevel) - 1) >> wlevel) > (1ull << 26)) wlevel++;
         for (;;) {

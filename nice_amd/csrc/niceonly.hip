@@ -1,11 +1,12 @@
 // niceonly.hip -- niceonly field processing on gfx950: the entry points of
-// kernels.h.  The kernel templates are in niceonly_kernels.hpp; this object
+// kernels.h.  The kernel templates are in niceonly_cand.hpp, niceonly_msd.hpp
+// and niceonly_wave.hpp, their launchers in niceonly_launch.hpp; this object
 // holds their run-time-base instantiations (any base 2..128, any n < 2^128),
 // the kernels without a base parameter, and the dispatch to the fast bases'
 // compile-time instantiations (niceonly_bases.h), which are built a few bases
 // per object from niceonly_part.hip.
 #include "niceonly_bases.h"
-#include "niceonly_kernels.hpp"
+#include "niceonly_launch.hpp"
 
 namespace nice {
 
@@ -57,92 +58,51 @@ bool sound_prefix_field(const MsdLaunch &p) {
     }
 }
 
+// One launch for any base: fast(BaseLaunch<b>{}, snd) runs a fast base's
+// compile-time kernels, generic(snd...) the run-time-base ones.  A sound field
+// that is not fast_ok, or whose base has no compile-time kernels, runs the
+// latter with the prefix test cleared.
+template <class Fast, class Generic>
+static hipError_t dispatch_base(u32 base, const SoundLaunch *snd, bool fast_ok, Fast fast, Generic generic) {
+    if (!snd || fast_ok) {
+        switch (base) {
+#define X(b) case b: return fast(BaseLaunch<b>{}, snd);
+            NICE_NICEONLY_BASES(X)
+#undef X
+        default: break;
+        }
+    }
+    if (!snd) return generic();
+    SoundLaunch off = *snd;
+    off.prefix_test = 0;
+    return generic(off);
+}
+
 hipError_t launch_niceonly(const NiceonlyLaunch &p, int num_cus, hipStream_t s, const SoundLaunch *snd) {
     if (!p.n_leaves_dev && p.n_leaves == 0 && !p.fin.done) return hipSuccess;
-    if (snd) {
-        if (snd->fast && p.n_leaves_dev) {
-            switch (p.base) {
-#define X(b) case b: return BaseLaunch<b>::nice_sound(p, num_cus, s, *snd);
-                NICE_NICEONLY_BASES(X)
-#undef X
-            default: break;
-            }
-        }
-        SoundLaunch off = *snd;
-        off.prefix_test = 0;
-        return launch_nice<GenericBase>(p, make_generic(p.base), num_cus, s, off);
-    }
-    switch (p.base) {
-#define X(b) case b: return BaseLaunch<b>::nice(p, num_cus, s);
-        NICE_NICEONLY_BASES(X)
-#undef X
-    default: return launch_nice(p, make_generic(p.base), num_cus, s);
-    }
+    return dispatch_base(
+        p.base, snd, snd && snd->fast && p.n_leaves_dev,
+        [&](auto b, const SoundLaunch *sn) { return decltype(b)::nice(p, num_cus, s, sn); },
+        [&](auto... off) { return launch_nice(p, make_generic(p.base), num_cus, s, off...); });
 }
 
 hipError_t launch_msd_wave(const MsdLaunch &p, const NiceonlyLaunch &c, uint32_t level0, void *scratch,
                            uint32_t grid, int num_cus, hipStream_t s, const SoundLaunch *snd) {
     if (level0 > 22 || (p.nchunks << level0) >> level0 != p.nchunks) return hipErrorInvalidValue;
     StackNode *st = (StackNode *)scratch;
-    if (snd) {
-        if (snd->fast) {
-            switch (p.base) {
-#define X(b) case b: return BaseLaunch<b>::wave_sound(p, c, level0, st, grid, num_cus, s, *snd);
-                NICE_NICEONLY_BASES(X)
-#undef X
-            default: break;
-            }
-        }
-        SoundLaunch off = *snd;
-        off.prefix_test = 0;
-        return launch_wave<GenericBase, 0>(p, c, level0, st, grid, make_generic(p.base), num_cus, s,
-                                                 off);
-    }
-    switch (p.base) {
-#define X(b) case b: return BaseLaunch<b>::wave(p, c, level0, st, grid, num_cus, s);
-        NICE_NICEONLY_BASES(X)
-#undef X
-    default: return launch_wave(p, c, level0, st, grid, make_generic(p.base), num_cus, s);
-    }
-}
-
-size_t msd_wave_scratch_bytes(uint32_t grid) { return (size_t)grid * (kWaveWG / 64) * kStackCap * sizeof(StackNode); }
-uint32_t msd_wave_waves_per_group() { return kWaveWG / 64; }
-
-u32 msd_fused_cap(u64 chunk, u64 floor_size) {
-    if (chunk > 0xffffffffull || floor_size == 0) return 0;
-    const u64 need = chunk / floor_size + 2;
-    if (need > kFusedMaxCap) return 0;
-    u32 cap = 64;
-    while (cap < need) cap <<= 1;
-    return cap;
+    return dispatch_base(
+        p.base, snd, snd && snd->fast,
+        [&](auto b, const SoundLaunch *sn) { return decltype(b)::wave(p, c, level0, st, grid, num_cus, s, sn); },
+        [&](auto... off) { return launch_wave(p, c, level0, st, grid, make_generic(p.base), num_cus, s, off...); });
 }
 
 hipError_t launch_msd_device(const MsdLaunch &p, int num_cus, hipStream_t s, ChunkNode *scratch,
                              u32 cap, u32 grid, const SoundLaunch *snd) {
     if (scratch && p.nchunks > 0xffffffffull) return hipErrorInvalidValue;
-    if (snd) {
-        if (snd->fast) {
-            switch (p.base) {
-#define X(b) case b: return BaseLaunch<b>::msd_sound(p, num_cus, s, scratch, cap, grid, *snd);
-                NICE_NICEONLY_BASES(X)
-#undef X
-            default: break;
-            }
-        }
-        SoundLaunch off = *snd;
-        off.prefix_test = 0;
-        if (scratch) return launch_fused<GenericBase, 0>(p, make_generic(p.base), scratch, cap, grid, s, off);
-        return launch_msd<GenericBase, 0>(p, make_generic(p.base), num_cus, s, off);
-    }
-    switch (p.base) {
-#define X(b) case b: return BaseLaunch<b>::msd(p, num_cus, s, scratch, cap, grid);
-        NICE_NICEONLY_BASES(X)
-#undef X
-    default:
-        if (scratch) return launch_fused(p, make_generic(p.base), scratch, cap, grid, s);
-        return launch_msd(p, make_generic(p.base), num_cus, s);
-    }
+    return dispatch_base(
+        p.base, snd, snd && snd->fast,
+        [&](auto b, const SoundLaunch *sn) { return decltype(b)::msd(p, num_cus, s, scratch, cap, grid, sn); },
+        [&](auto... off) { return launch_msd(p, make_generic(p.base), num_cus, s, scratch, cap, grid, off...); });
 }
 
 hipError_t launch_unique_fast(const uint64_t *n_pairs, uint32_t count, uint32_t base, uint32_t *out,

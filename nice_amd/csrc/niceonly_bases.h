@@ -4,7 +4,8 @@
 // niceonly fields return an empty list before any kernel runs.)
 //
 // Everything with a per-base compile-time niceonly path dispatches from it:
-//   * the device kernels (niceonly_kernels.hpp, instantiated per part in
+//   * the device kernels (niceonly_cand.hpp, niceonly_msd.hpp and
+//     niceonly_wave.hpp, instantiated per part in
 //     niceonly_part.hip: ConstBase divisors, radix_fast.hpp's in-range limb
 //     paths, the square-survivor queue, the LDS pair table, the lane walk);
 //   * the ABI hooks (abi_hooks.cpp) and nice_niceonly_fast_base

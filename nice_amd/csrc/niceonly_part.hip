@@ -4,7 +4,7 @@
 // msd_wave_kernel and unique_fast_kernel for the bases of
 // NICE_NICEONLY_PARTk (niceonly_bases.h), so they compile in parallel.
 #include "niceonly_bases.h"
-#include "niceonly_kernels.hpp"
+#include "niceonly_launch.hpp"
 
 #ifndef NICEONLY_PART
 #error "build with -DNICEONLY_PART=k"
@@ -25,33 +25,14 @@ static bool const_mod_field(const MsdLaunch &p) {
     return wide_n<B>() ? (p.end_hi >> kWideHiBits) == 0 : true;
 }
 
-template <int B>
-hipError_t BaseLaunch<B>::nice(const NiceonlyLaunch &p, int num_cus, hipStream_t s) {
-    return launch_nice(p, ConstBase<B>{}, num_cus, s);
-}
-
-template <int B>
-hipError_t BaseLaunch<B>::msd(const MsdLaunch &p, int num_cus, hipStream_t s, ChunkNode *scratch, u32 cap,
-                              u32 grid) {
-    if (scratch) {  // one workgroup per chunk, all levels in-kernel
-        if (const_mod_field<B>(p))
-            return launch_fused<ConstBase<B>, const_modulus<B>()>(p, ConstBase<B>{}, scratch, cap, grid, s);
-        return launch_fused(p, ConstBase<B>{}, scratch, cap, grid, s);
-    }
-    if (const_mod_field<B>(p)) return launch_msd<ConstBase<B>, const_modulus<B>()>(p, ConstBase<B>{}, num_cus, s);
-    return launch_msd(p, ConstBase<B>{}, num_cus, s);
-}
-
-template <int B>
-hipError_t BaseLaunch<B>::wave(const MsdLaunch &p, const NiceonlyLaunch &c, u32 level0, StackNode *scratch,
-                               u32 grid, int num_cus, hipStream_t s) {
-    if (const_mod_field<B>(p))
-        return launch_wave<ConstBase<B>, const_modulus<B>()>(p, c, level0, scratch, grid, ConstBase<B>{}, num_cus, s);
-    return launch_wave(p, c, level0, scratch, grid, ConstBase<B>{}, num_cus, s);
-}
-
-// Sound variants: one instantiation set per base -- the const-modulus one of a
-// two-word base, the plain one of a three-word base.
+// Sound variants (snd; niceonly.hip sends only sound_fast fields here): one
+// instantiation set per base -- the const-modulus one of a two-word base, the
+// plain one of a three-word base.
+// Each launcher below names the reference filter's instantiations before the
+// sound one.  The order matters to the build, not to the result: the compiler
+// emits a part's kernels in the order its host code first names them, and the
+// sound level and fused kernels of the two-word bases came out with other
+// instructions when they were named first.
 template <int B>
 bool BaseLaunch<B>::sound_fast(const MsdLaunch &p) {
     if (!p.in_range || p.M != (u32)(B - 1) * B * B) return false;
@@ -59,23 +40,33 @@ bool BaseLaunch<B>::sound_fast(const MsdLaunch &p) {
 }
 
 template <int B>
-hipError_t BaseLaunch<B>::nice_sound(const NiceonlyLaunch &p, int num_cus, hipStream_t s, const SoundLaunch &snd) {
-    return launch_nice<ConstBase<B>>(p, ConstBase<B>{}, num_cus, s, snd);
+hipError_t BaseLaunch<B>::nice(const NiceonlyLaunch &p, int num_cus, hipStream_t s, const SoundLaunch *snd) {
+    if (!snd) return launch_nice(p, ConstBase<B>{}, num_cus, s);
+    return launch_nice(p, ConstBase<B>{}, num_cus, s, *snd);
 }
 
 template <int B>
-hipError_t BaseLaunch<B>::msd_sound(const MsdLaunch &p, int num_cus, hipStream_t s, ChunkNode *scratch, u32 cap,
-                                    u32 grid, const SoundLaunch &snd) {
+hipError_t BaseLaunch<B>::msd(const MsdLaunch &p, int num_cus, hipStream_t s, ChunkNode *scratch, u32 cap, u32 grid,
+                              const SoundLaunch *snd) {
+    using G = ConstBase<B>;
     constexpr u32 MC = const_modulus<B>();
-    if (scratch) return launch_fused<ConstBase<B>, MC>(p, ConstBase<B>{}, scratch, cap, grid, s, snd);
-    return launch_msd<ConstBase<B>, MC>(p, ConstBase<B>{}, num_cus, s, snd);
+    if (!snd) {
+        if (const_mod_field<B>(p)) return launch_msd<G, MC>(p, G{}, num_cus, s, scratch, cap, grid);
+        return launch_msd<G, 0>(p, G{}, num_cus, s, scratch, cap, grid);
+    }
+    return launch_msd<G, MC>(p, G{}, num_cus, s, scratch, cap, grid, *snd);
 }
 
 template <int B>
-hipError_t BaseLaunch<B>::wave_sound(const MsdLaunch &p, const NiceonlyLaunch &c, u32 level0, StackNode *scratch,
-                                     u32 grid, int num_cus, hipStream_t s, const SoundLaunch &snd) {
-    return launch_wave<ConstBase<B>, const_modulus<B>()>(p, c, level0, scratch, grid, ConstBase<B>{}, num_cus, s,
-                                                               snd);
+hipError_t BaseLaunch<B>::wave(const MsdLaunch &p, const NiceonlyLaunch &c, u32 level0, StackNode *scratch,
+                               u32 grid, int num_cus, hipStream_t s, const SoundLaunch *snd) {
+    using G = ConstBase<B>;
+    constexpr u32 MC = const_modulus<B>();
+    if (!snd) {
+        if (const_mod_field<B>(p)) return launch_wave<G, MC>(p, c, level0, scratch, grid, G{}, num_cus, s);
+        return launch_wave<G, 0>(p, c, level0, scratch, grid, G{}, num_cus, s);
+    }
+    return launch_wave<G, MC>(p, c, level0, scratch, grid, G{}, num_cus, s, *snd);
 }
 
 template <int B>
