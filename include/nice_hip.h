@@ -312,6 +312,23 @@ int nice_debug_fd_window(uint32_t base, uint32_t *w0, uint32_t *w);
  * niceonly and nice_validate_detailed keep the production cutoff.  No device
  * needed to set it. */
 int nice_debug_set_near_miss_cutoff(uint32_t base, uint32_t cutoff);
+/* Test hook: every niceonly field of `base` submitted later in this process
+ * that lies wholly inside the base's valid range lists, from the compile-time
+ * kernels, every stride candidate whose square is repeat-free and whose digit
+ * union of n^2 and n^3 has >= nice_min members, instead of only the nice
+ * numbers (production compares with the base; in range the union cannot
+ * exceed it, so `== base` and `>= base` are the same).  The candidates, ranges
+ * and square_ok statistics do not change.  The listed entries keep
+ * num_uniques = base, as every niceonly entry does: the list says which
+ * numbers passed, not their counts.  The value is read once, when a field is
+ * submitted: a re-run after list growth and a collect after the hook was
+ * cleared still use it.  0 restores production for that base; valid non-zero
+ * values are 1..base.  NICE_ERR_INVALID for a base that is not a
+ * nice_niceonly_fast_base or a value above the base.  Fields that leave the
+ * valid range, the run-time-base kernels, nice_cpu_process_range_niceonly and
+ * nice_check_is_nice_inrange keep production semantics.  No device needed to
+ * set it. */
+int nice_debug_set_nice_min(uint32_t base, uint32_t nice_min);
 /* Test hook: the cpu.max cap nice_host_threads applies for the cgroup
  * `cgroup_path` under a cgroup2 mount at `root` (0 = no quota). */
 uint32_t nice_debug_cgroup_cpus(const char *root, const char *cgroup_path);
@@ -435,6 +452,12 @@ int nice_debug_is_nice(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t count, u
  * count its niceness test compares with the base. */
 int nice_debug_unique_fast(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t count, uint32_t base,
                            uint32_t *out);
+/* The niceonly kernels' cube pass (same bases and n): the count it compares
+ * with the base (or with nice_debug_set_nice_min's value) -- the members of the
+ * digit union of n^2 and n^3, 0 when n^2 repeats a digit -- through the LDS
+ * pair table for the two-word bases (b <= 64) and by VALU for b65, b68, b80. */
+int nice_debug_cube_count(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t count, uint32_t base,
+                          uint32_t *out);
 
 #ifdef __cplusplus
 }

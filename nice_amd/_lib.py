@@ -50,6 +50,7 @@ EXPORTS = (
     "nice_check_prefix_reject_inrange",
     "nice_process_ranges_detailed", "nice_last_ranges_stats", "nice_cpu_process_ranges_detailed",
     "nice_debug_ranges_plan", "nice_debug_set_near_miss_cutoff", "nice_debug_fd_window",
+    "nice_debug_set_nice_min", "nice_debug_cube_count",
 )
 
 
@@ -169,6 +170,8 @@ def lib():
         "nice_debug_force_sib_stride": ([u32], i32),
         "nice_debug_set_near_miss_cutoff": ([u32, u32], i32),
         "nice_debug_fd_window": ([u32, P32, P32], i32),
+        "nice_debug_set_nice_min": ([u32, u32], i32),
+        "nice_debug_cube_count": ([vp, P64, u32, u32, P32], i32),
         "nice_process_ranges_detailed": ([vp, u32, P64, sz, u32, P64, PN, P32, sz, PSZ], i32),
         "nice_last_ranges_stats": ([vp, ctypes.POINTER(nice_ranges_stats)], i32),
         "nice_cpu_process_ranges_detailed": ([u32, P64, sz, u32, i32, P64, PN, P32, sz, PSZ], i32),

@@ -420,6 +420,17 @@ class GpuContext:
         check(lib().nice_debug_unique_fast(self._h, arr, len(ns), base, out))
         return list(out[: len(ns)])
 
+    def debug_cube_count(self, ns: Sequence[int], base: int) -> List[int]:
+        """What the niceonly kernels' cube pass compares with the base: the
+        digit-union count of n^2 and n^3, 0 when n^2 repeats a digit (LDS pair
+        table for b <= 64, VALU above); every n in the base's valid range."""
+        arr = (ctypes.c_uint64 * (2 * max(len(ns), 1)))()
+        for i, n in enumerate(ns):
+            arr[2 * i], arr[2 * i + 1] = _split(n)
+        out = (ctypes.c_uint32 * max(len(ns), 1))()
+        check(lib().nice_debug_cube_count(self._h, arr, len(ns), base, out))
+        return list(out[: len(ns)])
+
     def debug_is_nice(self, ns: Sequence[int], base: int) -> List[bool]:
         arr = (ctypes.c_uint64 * (2 * max(len(ns), 1)))()
         for i, n in enumerate(ns):

@@ -92,6 +92,20 @@ int nice_debug_unique_fast(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t coun
     });
 }
 
+int nice_debug_cube_count(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t count, uint32_t base,
+                          uint32_t *out) {
+    u128 rs, re;
+    if (!ctx || !fast_base_range(base, rs, re))
+        return fail(NICE_ERR_INVALID, "base without a niceonly fast path");
+    for (uint32_t i = 0; i < count; i++) {
+        const u128 n = mk(n_pairs[2 * i], n_pairs[2 * i + 1]);
+        if (n < rs || n >= re) return fail(NICE_ERR_INVALID, "n outside the base's valid range");
+    }
+    return debug_per_n(ctx, n_pairs, count, out, [&](const uint64_t *dn, uint32_t *du, hipStream_t s) {
+        return nice::launch_cube_count(dn, count, base, du, s);
+    });
+}
+
 int nice_check_is_nice_inrange(uint32_t base, uint64_t lo, uint64_t hi) {
     u128 rs, re;
     const u128 n = mk(lo, hi);
@@ -219,6 +233,14 @@ int nice_debug_set_near_miss_cutoff(uint32_t base, uint32_t cutoff) {
         return fail(NICE_ERR_INVALID, "cutoff must be 0 (production) or in [" + std::to_string(w0 + w - 1) + ", " +
                                           std::to_string(base - 1) + "]");
     g_cutoff_override[base].store(cutoff, std::memory_order_relaxed);
+    return NICE_OK;
+}
+
+int nice_debug_set_nice_min(uint32_t base, uint32_t nice_min) {
+    if (!nice::niceonly_fast_base(base)) return fail(NICE_ERR_INVALID, "base without a niceonly fast path");
+    if (nice_min > base)
+        return fail(NICE_ERR_INVALID, "nice_min must be 0 (production) or in [1, " + std::to_string(base) + "]");
+    g_nice_min_override[base].store(nice_min, std::memory_order_relaxed);
     return NICE_OK;
 }
 

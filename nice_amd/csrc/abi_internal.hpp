@@ -193,6 +193,8 @@ struct NiceJob {
     bool adapt = false;            // host-MSD field on the adaptive floor: update it at collect
     uint32_t reruns = 0;           // times the field was re-run with grown device lists
     uint64_t rejected = 0;         // sound filter: candidates the prefix test rejected
+    uint32_t nice_min = 0;         // nice_debug_set_nice_min's value for the base when the field was
+                                   // submitted (0: production); a re-run keeps it
 };
 
 // nice_process_ranges_detailed: one stream and its buffers per device, apart
@@ -349,6 +351,11 @@ inline uint32_t effective_cutoff(uint32_t base) {
     const uint32_t c = base <= 128 ? g_cutoff_override[base].load(std::memory_order_relaxed) : 0u;
     return c ? c : near_miss_cutoff(base);
 }
+
+// nice_debug_set_nice_min: per base, the union count from which the compile-time
+// niceonly kernels list a square survivor of an in-range field (0: production,
+// the base).  Read once per field, at submit (NiceJob::nice_min).
+inline std::atomic<uint32_t> g_nice_min_override[129];
 
 // The server's submit invariants for a detailed result (api/src/main.rs:
 // 309-359): the distribution sums to the field size; for every bin above the

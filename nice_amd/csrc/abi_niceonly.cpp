@@ -32,6 +32,7 @@ struct NiceField {
     bool empty = false;  // nothing to run (residue-empty base, no chunk dealt): nothing below is set
     std::shared_ptr<nice::StrideTable> table;
     uint32_t in_range = 0;  // the whole field inside the base's valid range
+    uint32_t nice_min = 0;  // NiceonlyLaunch::nice_min: the base, or the job's lowered value (in range)
     uint32_t R = 0, M = 0;  // residues per cycle, stride modulus
 
     // the tables' key in Device::residues / ranks / lowtabs
@@ -72,6 +73,7 @@ int resolve_field(const NiceJob &job, NiceField &f) {
     // fixed-digit-count fast paths (radix_fast.hpp).
     u128 vr_s = 0, vr_e = 0;
     f.in_range = nice::base_range_cached(f.base, vr_s, vr_e) == 1 && vr_s <= f.s && f.e <= vr_e ? 1u : 0u;
+    f.nice_min = f.in_range && job.nice_min ? job.nice_min : f.base;
     f.R = (uint32_t)f.table->residues.size();
     if (f.table->modulus > 0xffffffffull) return fail(NICE_ERR_INVALID, "stride modulus exceeds u32");
     f.M = (uint32_t)f.table->modulus;
@@ -163,7 +165,8 @@ nice::NiceonlyLaunch candidate_launch(const NiceField &f, Device &d, Slot &sl) {
     p.M = f.M;
     p.base = f.base;
     p.in_range = f.in_range;
-    p.out = nice::NumOut{sl.nice.n, nullptr, sl.d_nice_count, sl.nice.cap};
+    p.nice_min = f.nice_min;
+    p.out =nice::NumOut{sl.nice.n, nullptr, sl.d_nice_count, sl.nice.cap};
     return p;
 }
 
@@ -564,6 +567,7 @@ int niceonly_submit_args(nice_ctx *ctx, uint64_t start_lo, uint64_t start_hi, ui
     job.has_opts = opts != nullptr;
     if (opts) job.opts = *opts;
     job.st.msd_floor = floor_size;
+    job.nice_min = g_nice_min_override[base].load(std::memory_order_relaxed);
     job.t0 = t0;
     const int rc = niceonly_enqueue(ctx, t, job);
     if (rc) return rc;

@@ -141,6 +141,9 @@ struct NiceonlyLaunch {
     uint32_t R, M;
     uint32_t base;
     uint32_t in_range;             // every candidate inside the base's valid range
+    uint32_t nice_min;             // in-range fields of the compile-time kernels: a square survivor is
+                                   // listed when its digit union has >= nice_min members (production:
+                                   // base, i.e. nice; nice_debug_set_nice_min lowers it)
     NumOut out;
     NiceFinish fin;
 };
@@ -237,5 +240,10 @@ hipError_t launch_is_nice(const uint64_t *n_pairs, uint32_t count, uint32_t base
 // count by niceonly_kernel's limb path (radix_fast.hpp unique_fast).
 hipError_t launch_unique_fast(const uint64_t *n_pairs, uint32_t count, uint32_t base,
                               uint32_t *out, hipStream_t s);
+// ... and the count the niceonly kernels' cube pass compares with
+// NiceonlyLaunch::nice_min (niceonly_cand.hpp cube_count: the LDS pair table
+// for the two-word bases, VALU for b65/68/80; 0 when n^2 repeats a digit).
+hipError_t launch_cube_count(const uint64_t *n_pairs, uint32_t count, uint32_t base,
+                             uint32_t *out, hipStream_t s);
 
 }  // namespace nice

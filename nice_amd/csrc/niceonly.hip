@@ -115,6 +115,16 @@ hipError_t launch_unique_fast(const uint64_t *n_pairs, uint32_t count, uint32_t 
     }
 }
 
+hipError_t launch_cube_count(const uint64_t *n_pairs, uint32_t count, uint32_t base, uint32_t *out,
+                             hipStream_t s) {
+    switch (base) {
+#define X(b) case b: return BaseLaunch<b>::cube(n_pairs, count, out, s);
+        NICE_NICEONLY_BASES(X)
+#undef X
+    default: return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_is_nice(const uint64_t *n_pairs, uint32_t count, uint32_t base, uint32_t *out,
                           hipStream_t s) {
     hipLaunchKernelGGL(is_nice_kernel, dim3((count + 255) / 256), dim3(256), 0, s, n_pairs, count,

@@ -203,16 +203,21 @@ __device__ __forceinline__ void pair_tab_fill(uint2 *tab) {
 // (the MSD filter already vetted the leading digits), yet nearly every round of
 // 64 holds one: testing the cube in place ran the 220-instruction cube for
 // almost every wave and round.  Queued, it runs once per 64 survivors.
+// A queued n is listed when the digit union of n^2 and n^3 (cube_count: 0 when
+// n^2 repeats a digit) has at least p.nice_min members: b in production, which
+// in range is "exactly b"; nice_debug_set_nice_min lowers it for the tests.
+template <int B>
+__device__ __forceinline__ u32 cube_count(u64 n_lo, u64 n_hi, const uint2 *tab) {
+    if constexpr (B > 32 && B <= 64) return nice_count_tab<B>(n_lo, n_hi, tab);
+    else return nice_count_fast<B>(n_lo, n_hi);
+}
 template <int B>
 __device__ __forceinline__ void cube_pass(const NiceonlyLaunch &p, const ulonglong2 *q, u32 head, u32 cnt,
                                           u32 lane, const uint2 *tab) {
     wave_sync_lds();  // the queue was written by other lanes of this wave
     if (lane < cnt) {
         const ulonglong2 e = q[(head + lane) & (kCubeQ - 1)];
-        bool nice;
-        if constexpr (B > 32 && B <= 64) nice = is_nice_tab<B>(e.x, e.y, tab);
-        else nice = is_nice_fast<B>(e.x, e.y);
-        if (nice) emit_nice(p, e.x, e.y);
+        if (cube_count<B>(e.x, e.y, tab) >= p.nice_min) emit_nice(p, e.x, e.y);
     }
     wave_sync_lds();
 }

@@ -67,6 +67,16 @@ __global__ void unique_fast_kernel(const u64 *n_pairs, u32 count, u32 *out) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) out[i] = unique_fast<B>(n_pairs[2 * i], n_pairs[2 * i + 1]);
 }
+// ... and the cube pass's count (cube_count, niceonly_cand.hpp), per n: the
+// pair table filled as niceonly_kernel fills it.
+template <int B>
+__global__ void __launch_bounds__(256) cube_count_kernel(const u64 *n_pairs, u32 count, u32 *out) {
+    using G = ConstBase<B>;
+    __shared__ uint2 tab[PairTab<G>::N];
+    pair_tab_fill<G>(tab);  // (ends with a barrier)
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) out[i] = cube_count<B>(n_pairs[2 * i], n_pairs[2 * i + 1], tab);
+}
 
 // The launchers of one fast base (niceonly_bases.h), defined and instantiated
 // in that base's part object (niceonly_part.hip); niceonly.hip dispatches.
@@ -84,6 +94,7 @@ struct BaseLaunch {
     static hipError_t wave(const MsdLaunch &p, const NiceonlyLaunch &c, u32 level0, StackNode *scratch, u32 grid,
                            int num_cus, hipStream_t s, const SoundLaunch *snd);
     static hipError_t unique(const u64 *n_pairs, u32 count, u32 *out, hipStream_t s);
+    static hipError_t cube(const u64 *n_pairs, u32 count, u32 *out, hipStream_t s);
 };
 
 }  // namespace nice

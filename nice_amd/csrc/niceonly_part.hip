@@ -1,7 +1,7 @@
 // niceonly_part.hip -- the niceonly kernels of the fast bases, one object per
 // part (built with -DNICEONLY_PART=k, k < NICEONLY_NPARTS): part k
 // instantiates niceonly_kernel, msd_level_kernel, msd_fused_kernel,
-// msd_wave_kernel and unique_fast_kernel for the bases of
+// msd_wave_kernel, unique_fast_kernel and cube_count_kernel for the bases of
 // NICE_NICEONLY_PARTk (niceonly_bases.h), so they compile in parallel.
 #include "niceonly_bases.h"
 #include "niceonly_launch.hpp"
@@ -72,6 +72,12 @@ hipError_t BaseLaunch<B>::wave(const MsdLaunch &p, const NiceonlyLaunch &c, u32 
 template <int B>
 hipError_t BaseLaunch<B>::unique(const u64 *n_pairs, u32 count, u32 *out, hipStream_t s) {
     hipLaunchKernelGGL(unique_fast_kernel<B>, dim3((count + 255) / 256), dim3(256), 0, s, n_pairs, count, out);
+    return hipGetLastError();
+}
+
+template <int B>
+hipError_t BaseLaunch<B>::cube(const u64 *n_pairs, u32 count, u32 *out, hipStream_t s) {
+    hipLaunchKernelGGL(cube_count_kernel<B>, dim3((count + 255) / 256), dim3(256), 0, s, n_pairs, count, out);
     return hipGetLastError();
 }
 

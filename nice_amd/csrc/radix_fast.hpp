@@ -214,18 +214,26 @@ __device__ __forceinline__ u32 limbs_popcount_tab(const u32 (&A)[N], int D, u32 
 // digits has b members": no per-digit test or branch, one popcount after n^2
 // (a repeat there ends it; the cube is multiplied out only for the ~1-2 % of
 // stride candidates whose square is repeat-free) and one after n^3.
+//
+// nice_count_*: the members of that union, or 0 when n^2 repeats a digit --
+// what the niceness test compares with b (and the cube pass of the niceonly
+// kernels with NiceonlyLaunch::nice_min, which is b in production).
 template <int BASE>
-__host__ __device__ __forceinline__ bool is_nice_limbs(const u32 (&X)[Radix<BASE>::NX]) {
+__host__ __device__ __forceinline__ u32 nice_count_limbs(const u32 (&X)[Radix<BASE>::NX]) {
     using R = Radix<BASE>;
     u32 S[R::NS];
     square_limbs<BASE>(X, S);
     u32 m[R::MW];
 #pragma unroll
     for (int w = 0; w < R::MW; w++) m[w] = 0;
-    if (limbs_popcount<BASE>(S, R::D2, m) != (u32)R::D2) return false;
+    if (limbs_popcount<BASE>(S, R::D2, m) != (u32)R::D2) return 0;
     u32 C[R::NC];
     cube_limbs<BASE>(S, X, C);
-    return limbs_popcount<BASE>(C, R::D3, m) == (u32)BASE;
+    return limbs_popcount<BASE>(C, R::D3, m);
+}
+template <int BASE>
+__host__ __device__ __forceinline__ bool is_nice_limbs(const u32 (&X)[Radix<BASE>::NX]) {
+    return nice_count_limbs<BASE>(X) == (u32)BASE;
 }
 
 // First half of is_nice_limbs: n^2 repeat-free (the stride candidates that
@@ -243,10 +251,14 @@ __host__ __device__ __forceinline__ bool square_ok(u64 lo, u64 hi) {
 }
 
 template <int BASE>
-__host__ __device__ __forceinline__ bool is_nice_fast(u64 lo, u64 hi) {
+__host__ __device__ __forceinline__ u32 nice_count_fast(u64 lo, u64 hi) {
     u32 X[Radix<BASE>::NX];
     to_limbs<BASE>(lo, hi, X);
-    return is_nice_limbs<BASE>(X);
+    return nice_count_limbs<BASE>(X);
+}
+template <int BASE>
+__host__ __device__ __forceinline__ bool is_nice_fast(u64 lo, u64 hi) {
+    return nice_count_fast<BASE>(lo, hi) == (u32)BASE;
 }
 
 // The same two tests with the LDS pair table (two-word bases, see above).
@@ -266,16 +278,16 @@ __device__ __forceinline__ bool square_ok_tab(u64 lo, u64 hi, const uint2 *tab) 
     return square_ok_tab_limbs<BASE>(X, tab);
 }
 template <int BASE>
-__device__ __forceinline__ bool is_nice_tab(u64 lo, u64 hi, const uint2 *tab) {
+__device__ __forceinline__ u32 nice_count_tab(u64 lo, u64 hi, const uint2 *tab) {
     using R = Radix<BASE>;
     static_assert(R::MW == 2, "pair table: two-word bases");
     u32 X[R::NX], S[R::NS], C[R::NC];
     to_limbs<BASE>(lo, hi, X);
     square_limbs<BASE>(X, S);
     u32 m[2] = {0, 0};
-    if (limbs_popcount_tab<BASE>(S, R::D2, m, tab) != (u32)R::D2) return false;
+    if (limbs_popcount_tab<BASE>(S, R::D2, m, tab) != (u32)R::D2) return 0;
     cube_limbs<BASE>(S, X, C);
-    return limbs_popcount_tab<BASE>(C, R::D3, m, tab) == (u32)BASE;
+    return limbs_popcount_tab<BASE>(C, R::D3, m, tab);
 }
 
 // Unique-digit count of in-range n by the same limb path (test hook: checks

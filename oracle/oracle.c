@@ -401,11 +401,12 @@ typedef struct {
     u64 *cand_counts;
     u64 *range_counts;
     u64 *sq_counts; /* test statistic: candidates whose square has no repeat (or NULL) */
+    u32 nice_min;   /* niceonly: 0 lists the nice numbers, else see niceonly_range_impl */
 } job;
 
 static uint64_t niceonly_range_impl(u128 s, u128 e, u32 base, const u64 *res, u64 R,
                                     u64 M, u64 floor_size, misslist *out, u64 *n_ranges,
-                                    u64 *n_sq);
+                                    u64 *n_sq, u32 nice_min);
 
 static void *worker(void *arg) {
     job *j = (job *)arg;
@@ -421,7 +422,8 @@ static void *worker(void *arg) {
                                                     j->stride_count, j->stride_mod,
                                                     j->floor_size, &j->lists[i],
                                                     &j->range_counts[i],
-                                                    j->sq_counts ? &j->sq_counts[i] : NULL);
+                                                    j->sq_counts ? &j->sq_counts[i] : NULL,
+                                                    j->nice_min);
         }
     }
     return NULL;
@@ -681,10 +683,14 @@ u64 oracle_valid_ranges(u64 slo, u64 shi, u64 elo, u64 ehi, u32 base, u64 floor_
     return n;
 }
 
-/* client_process.rs:439-465 + stride_filter.rs:139-155 */
+/* client_process.rs:439-465 + stride_filter.rs:139-155.
+ * nice_min (not part of the restatement; the checker of the GPU test hook
+ * nice_debug_set_nice_min): 0 lists the nice numbers, with u = base.  Otherwise
+ * a candidate is listed iff its square has no repeated digit and
+ * num_unique_digits(n) >= nice_min, with u = that count. */
 static uint64_t niceonly_range_impl(u128 s, u128 e, u32 base, const u64 *res, u64 R,
                                     u64 M, u64 floor_size, misslist *out, u64 *n_ranges,
-                                    u64 *n_sq) {
+                                    u64 *n_sq, u32 nice_min) {
     if (n_ranges) *n_ranges = 0;
     if (n_sq) *n_sq = 0;
     if (R == 0) return 0;
@@ -698,14 +704,19 @@ static uint64_t niceonly_range_impl(u128 s, u128 e, u32 base, const u64 *res, u6
         while (n < rl.e[q]) {
             cands++;
             int nice;
-            if (n_sq) {
+            u32 u = base;
+            if (n_sq || nice_min) {
                 int sq_ok = 0;
                 nice = is_nice_impl2(n, base, &sq_ok);
-                *n_sq += (u64)sq_ok;
+                if (n_sq) *n_sq += (u64)sq_ok;
+                if (nice_min) {
+                    u = sq_ok ? nud(n, base) : 0;
+                    nice = sq_ok && u >= nice_min;
+                }
             } else {
                 nice = is_nice(n, base);
             }
-            if (nice) ml_push(out, n, base);
+            if (nice) ml_push(out, n, u);
             n += (idx + 1 < R) ? res[idx + 1] - res[idx] : M - res[idx] + res[0];
             idx = (idx + 1) % R;
         }
@@ -736,7 +747,7 @@ u64 oracle_process_range_niceonly(u64 slo, u64 shi, u64 elo, u64 ehi, u32 base, 
     u64 *res = stride_table_alloc(base, k, &R, &M);
     misslist ml = {0};
     u64 c = niceonly_range_impl(mk(slo, shi), mk(elo, ehi), base, res, R, M, floor_size, &ml,
-                                NULL, NULL);
+                                NULL, NULL, 0);
     if (n_candidates) *n_candidates = c;
     u64 n = emit_nice(&ml, out, cap);
     free(ml.n); free(ml.u); free(res);
@@ -766,9 +777,21 @@ u64 oracle_process_field_niceonly_ex(u64 slo, u64 shi, u64 elo, u64 ehi, u32 bas
 u64 oracle_process_field_niceonly_sq(u64 slo, u64 shi, u64 elo, u64 ehi, u32 base,
                                      int threads, u64 chunk, u64 floor_size, u64 *out,
                                      u64 cap, u64 *n_candidates, u64 *n_ranges, u64 *n_sq) {
+    return oracle_process_field_niceonly_min(slo, shi, elo, ehi, base, threads, chunk, floor_size,
+                                             0, out, NULL, cap, n_candidates, n_ranges, n_sq);
+}
+
+/* _sq with a threshold (see niceonly_range_impl; 0: _sq's behaviour) and, when
+ * out_u is not NULL, each listed number's num_unique_digits (base at
+ * nice_min 0). */
+u64 oracle_process_field_niceonly_min(u64 slo, u64 shi, u64 elo, u64 ehi, u32 base,
+                                      int threads, u64 chunk, u64 floor_size, u32 nice_min,
+                                      u64 *out, u32 *out_u, u64 cap, u64 *n_candidates,
+                                      u64 *n_ranges, u64 *n_sq) {
     job j;
     memset(&j, 0, sizeof(j));
     j.start = mk(slo, shi); j.end = mk(elo, ehi); j.base = base; j.mode = 1;
+    j.nice_min = nice_min;
     j.floor_size = floor_size ? floor_size : 250; /* MSD_RECURSIVE_MIN_RANGE_SIZE, msd_prefix_filter.rs:282 */
     j.chunk = chunk ? (u128)chunk : client_chunk_size(j.end - j.start);
     j.nchunks = (u64)((j.end - j.start + j.chunk - 1) / j.chunk);
@@ -783,7 +806,7 @@ u64 oracle_process_field_niceonly_sq(u64 slo, u64 shi, u64 elo, u64 ehi, u32 bas
     u64 cands = 0, ranges = 0, sqs = 0;
     for (u64 i = 0; i < j.nchunks; i++) {
         for (size_t q = 0; q < j.lists[i].len; q++)
-            ml_push(&all, mk(j.lists[i].n[2 * q], j.lists[i].n[2 * q + 1]), base);
+            ml_push(&all, mk(j.lists[i].n[2 * q], j.lists[i].n[2 * q + 1]), j.lists[i].u[q]);
         cands += j.cand_counts[i];
         ranges += j.range_counts[i];
         if (j.sq_counts) sqs += j.sq_counts[i];
@@ -793,6 +816,7 @@ u64 oracle_process_field_niceonly_sq(u64 slo, u64 shi, u64 elo, u64 ehi, u32 bas
     if (n_ranges) *n_ranges = ranges;
     if (n_sq) *n_sq = sqs;
     u64 n = emit_nice(&all, out, cap);
+    for (u64 i = 0; out_u && i < all.len && i < cap; i++) out_u[i] = all.u[i];
     free(all.n); free(all.u); free(j.lists); free(j.cand_counts); free(j.range_counts);
     free(j.sq_counts);
     free(j.stride_res);

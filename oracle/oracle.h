@@ -142,6 +142,17 @@ uint64_t oracle_process_field_niceonly_sq(uint64_t start_lo, uint64_t start_hi,
                                           int threads, uint64_t chunk, uint64_t floor_size,
                                           uint64_t *out, uint64_t cap, uint64_t *n_candidates,
                                           uint64_t *n_ranges, uint64_t *n_sq);
+/* _sq with a threshold -- not part of the restatement: the checker of the GPU
+ * test hook nice_debug_set_nice_min.  nice_min 0 is _sq (out_u, if given, holds
+ * base).  Otherwise a stride candidate is listed iff its square has no
+ * repeated digit and oracle_num_unique_digits(n) >= nice_min; out_u (may be
+ * NULL) receives that count per listed number. */
+uint64_t oracle_process_field_niceonly_min(uint64_t start_lo, uint64_t start_hi,
+                                           uint64_t end_lo, uint64_t end_hi, uint32_t base,
+                                           int threads, uint64_t chunk, uint64_t floor_size,
+                                           uint32_t nice_min, uint64_t *out, uint32_t *out_u,
+                                           uint64_t cap, uint64_t *n_candidates,
+                                           uint64_t *n_ranges, uint64_t *n_sq);
 
 #ifdef __cplusplus
 }

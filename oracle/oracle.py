@@ -83,6 +83,9 @@ def lib():
         L.oracle_process_field_niceonly_sq.argtypes = [u64, u64, u64, u64, u32, i32, u64, u64,
                                                        P64, u64, P64, P64, P64]
         L.oracle_process_field_niceonly_sq.restype = u64
+        L.oracle_process_field_niceonly_min.argtypes = [u64, u64, u64, u64, u32, i32, u64, u64, u32,
+                                                        P64, P32, u64, P64, P64, P64]
+        L.oracle_process_field_niceonly_min.restype = u64
         _lib = L
     return _lib
 
@@ -240,16 +243,31 @@ def process_field_niceonly_ex(start: int, end: int, base: int, threads: int, chu
 
 
 def process_field_niceonly_sq(start: int, end: int, base: int, threads: int, chunk: int = 0,
-                              floor_size: int = 0, cap: int = 1 << 16):
+                              floor_size: int = 0, cap: int = 1 << 16, nice_min: int = 0):
     """process_field_niceonly_ex plus the number of stride candidates whose
     square alone has no repeated digit (get_is_nice reached the cube scan): a
     test statistic for the GPU's square-survivor count.  Returns
-    (FieldResults, candidates, ranges, square_ok)."""
-    buf = (ctypes.c_uint64 * (2 * cap))()
+    (FieldResults, candidates, ranges, square_ok).
+
+    nice_min (the checker of the GPU hook nice_debug_set_nice_min; 0, the
+    default, is the reference's list): a candidate is listed iff its square
+    has no repeated digit and num_unique_digits(n) >= nice_min, and the
+    entries carry that count instead of base."""
     cands, ranges, sq = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-    n = lib().oracle_process_field_niceonly_sq(*_split(start), *_split(end), base, threads, chunk,
-                                               floor_size, buf, cap, cands, ranges, sq)
-    if n > cap:
-        raise OverflowError("nice list exceeded capacity")
-    nice = [(buf[2 * i] | (buf[2 * i + 1] << 64), base) for i in range(n)]
+    if not nice_min:
+        buf = (ctypes.c_uint64 * (2 * cap))()
+        n = lib().oracle_process_field_niceonly_sq(*_split(start), *_split(end), base, threads, chunk,
+                                                   floor_size, buf, cap, cands, ranges, sq)
+        if n > cap:
+            raise OverflowError("nice list exceeded capacity")
+        nice = [(buf[2 * i] | (buf[2 * i + 1] << 64), base) for i in range(n)]
+        return FieldResults([], nice), cands.value, ranges.value, sq.value
+    while True:
+        buf, ubuf = (ctypes.c_uint64 * (2 * cap))(), (ctypes.c_uint32 * cap)()
+        n = lib().oracle_process_field_niceonly_min(*_split(start), *_split(end), base, threads, chunk,
+                                                    floor_size, nice_min, buf, ubuf, cap, cands, ranges, sq)
+        if n <= cap:
+            break
+        cap = n  # a lowered threshold lists many: once more with room
+    nice = [(buf[2 * i] | (buf[2 * i + 1] << 64), ubuf[i]) for i in range(n)]
     return FieldResults([], nice), cands.value, ranges.value, sq.value

@@ -92,15 +92,19 @@ def oracle_ranges(a, e, base, floor, filter_c, chunk=0):
     return out
 
 
+def union_count(n, base):
+    """Members of the digit union of n^2 and n^3."""
+    return len(set(digits(n * n, base)) | set(digits(n ** 3, base)))
+
+
 @functools.lru_cache(maxsize=None)
-def sound_field(a, size, base, chunk, floor=250):
-    """What a sound niceonly field of [a, a + size) must report: (ranges,
-    candidates, prefix_rejected, square_ok, nice list).  Ranges, candidates and
-    the list are the oracle's with Filter C off; the rejected and square counts
-    come from the restatement above."""
+def _sound_core(a, size, base, chunk, floor):
+    """(ranges, candidates, prefix_rejected, the kept candidates whose square
+    is repeat-free, the oracle's nice list) of the sound field [a, a + size)."""
     leaves = oracle_ranges(a, a + size, base, floor, False, chunk)
     res, cands, ranges, _ = O.process_field_niceonly_sq(a, a + size, base, 16, chunk, floor)
-    n_cand = n_rej = n_sq = 0
+    n_cand = n_rej = 0
+    kept = []
     for s, e in leaves:
         pre = leaf_prefix(s, e, base)
         for n in candidates(s, e, base):
@@ -108,6 +112,21 @@ def sound_field(a, size, base, chunk, floor=250):
             if rejected(pre, n, base):
                 n_rej += 1
             elif square_repeat_free(n, base):
-                n_sq += 1
+                kept.append(n)
     assert (len(leaves), n_cand) == (ranges, cands)
-    return ranges, cands, n_rej, n_sq, [n for n, _ in res.nice_numbers]
+    return ranges, cands, n_rej, tuple(kept), [n for n, _ in res.nice_numbers]
+
+
+def sound_field(a, size, base, chunk, floor=250, nice_min=0):
+    """What a sound niceonly field of [a, a + size) must report: (ranges,
+    candidates, prefix_rejected, square_ok, nice list).  Ranges, candidates and
+    the list are the oracle's with Filter C off; the rejected and square counts
+    come from the restatement above.
+
+    nice_min (nice_debug_set_nice_min's threshold; 0: production): the list
+    holds instead every candidate the prefix test keeps whose square is
+    repeat-free and whose union_count is >= nice_min, by the restatement."""
+    ranges, cands, n_rej, kept, nice = _sound_core(a, size, base, chunk, floor)
+    if nice_min:
+        nice = sorted(n for n in kept if union_count(n, base) >= nice_min)
+    return ranges, cands, n_rej, len(kept), list(nice)
