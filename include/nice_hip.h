@@ -271,6 +271,7 @@ typedef struct {
     uint64_t numbers;    /* numbers processed by those launches */
     uint32_t sib_lanes;  /* sibling lanes M of the FD kernel's last sibling-lane launch (0: none ran) */
     uint32_t sib_stride; /* ... and its lane stride L */
+    uint32_t sib_grid;   /* ... and the workgroups of its persistent sibling grid (0: rounds of workgroups) */
 } nice_kernel_stats;
 int nice_last_kernel_stats(nice_ctx *ctx, int device_index, nice_kernel_stats *out);
 /* Kernel timing of later detailed fields on this context (default on): with
@@ -292,6 +293,12 @@ uint32_t nice_host_threads(void);
  * model's pick, and fields of >= 4 super-blocks take the sibling kernel
  * whatever their size; 0 restores production.  NICE_ERR_INVALID otherwise. */
 int nice_debug_force_sib_stride(uint32_t L);
+/* Test hook: the persistent grid of the FD kernel's sibling-lane launches in
+ * this process (b40, first limb layout).  mode 0: production (the planner's
+ * threshold decides); 1: every sibling-lane segment of >= 4 super-blocks runs
+ * on it, with at most max_workgroups workgroups when that is nonzero; 2: never
+ * (rounds of workgroups).  NICE_ERR_INVALID for another mode. */
+int nice_debug_force_sib_persistent(uint32_t mode, uint32_t max_workgroups);
 /* Test hook: the compile-time histogram window [w0, w0 + w) of the FD kernel
  * of `base`: unique counts inside it are counted in LDS, the others take the
  * kernel's out-of-window branch, which also lists the near-misses.

@@ -50,7 +50,7 @@ EXPORTS = (
     "nice_check_prefix_reject_inrange",
     "nice_process_ranges_detailed", "nice_last_ranges_stats", "nice_cpu_process_ranges_detailed",
     "nice_debug_ranges_plan", "nice_debug_set_near_miss_cutoff", "nice_debug_fd_window",
-    "nice_debug_set_nice_min", "nice_debug_cube_count",
+    "nice_debug_set_nice_min", "nice_debug_cube_count", "nice_debug_force_sib_persistent",
 )
 
 
@@ -87,7 +87,8 @@ class nice_niceonly_stats(ctypes.Structure):
 class nice_kernel_stats(ctypes.Structure):
     _fields_ = [("kernel_ms", ctypes.c_double), ("launches", ctypes.c_uint32),
                 ("fd_kernel", ctypes.c_uint32), ("numbers", ctypes.c_uint64),
-                ("sib_lanes", ctypes.c_uint32), ("sib_stride", ctypes.c_uint32)]
+                ("sib_lanes", ctypes.c_uint32), ("sib_stride", ctypes.c_uint32),
+                ("sib_grid", ctypes.c_uint32)]
 
 
 class nice_ranges_stats(ctypes.Structure):
@@ -168,6 +169,7 @@ def lib():
         "nice_host_threads": ([], u32),
         "nice_debug_cgroup_cpus": ([ctypes.c_char_p, ctypes.c_char_p], u32),
         "nice_debug_force_sib_stride": ([u32], i32),
+        "nice_debug_force_sib_persistent": ([u32, u32], i32),
         "nice_debug_set_near_miss_cutoff": ([u32, u32], i32),
         "nice_debug_fd_window": ([u32, P32, P32], i32),
         "nice_debug_set_nice_min": ([u32, u32], i32),

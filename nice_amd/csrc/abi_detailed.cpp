@@ -133,7 +133,7 @@ int enqueue_detailed_shard(Device &d, Slot &sl, u128 s, u128 e, uint32_t base, b
     }
     sl.seq++;
     sl.launches = 0;
-    sl.sib[0] = sl.sib[1] = 0;
+    sl.sib[0] = sl.sib[1] = sl.sib[2] = 0;
     // The state block is zeroed by the previous field's finish; a memset
     // only after an interrupted field (or the first one).
     if (sl.dirty) HIPCHK(hipMemsetAsync(sl.d_state, 0, kStateBytes, sl.stream));
@@ -208,6 +208,7 @@ uint32_t shard_finished(Device &d, Slot &sl, int t) {
     d.last.launches = sl.launches;
     d.last.sib_lanes = sl.sib[0];
     d.last.sib_stride = sl.sib[1];
+    d.last.sib_grid = sl.sib[2];
     return (uint32_t)sl.h_fin[nice::kFinCount];
 }
 

@@ -218,6 +218,12 @@ int nice_debug_force_sib_stride(uint32_t L) {
     return NICE_OK;
 }
 
+int nice_debug_force_sib_persistent(uint32_t mode, uint32_t max_workgroups) {
+    if (mode > 2) return fail(NICE_ERR_INVALID, "mode must be 0 (production), 1 (persistent) or 2 (rounds)");
+    nice::fd2_force_sib_persistent(mode, max_workgroups);
+    return NICE_OK;
+}
+
 int nice_debug_fd_window(uint32_t base, uint32_t *w0, uint32_t *w) {
     if (!w0 || !w) return fail(NICE_ERR_INVALID, "null argument");
     if (!nice::fd2_window(base, w0, w)) return fail(NICE_ERR_INVALID, "base has no FD kernel");

@@ -134,7 +134,7 @@ struct Slot {
     bool marked = false;          // ... or an untimed end marker (ev_done) on a shared stream
     uint64_t seq = 0;             // last detailed field's sequence number
     uint32_t launches = 0;        // ... and its kernel launches (the finish kernel not counted)
-    uint32_t sib[2] = {0, 0};     // ... and its last sibling-lane launch: lanes M, stride L
+    uint32_t sib[3] = {0, 0, 0};  // ... and its last sibling-lane launch: lanes M, stride L, persistent grid
     bool fin_seq = false;         // ... and whether its fd2 finish publishes it
     uint32_t tag = 0;             // ... as tagged words (FieldFinish::tag; 0: bins + sequence word)
     uint32_t tag_words = 0;       // ... bins 0..tag_words-1 (and kFinCount) carry the tag

@@ -401,9 +401,21 @@ struct Cfg {
     // n + j B^2 agree mod B^2, so limbs 0 and 1 of n^2, n^3, 2n + 1 and 3n + 1
     // (radix B) are the same for all of them and so is the carry out of limb
     // 1 of every chain: the low-digit lookup, limb 1's two lookups and limb 1's
-    // carry chains run once for the M numbers (walk_sib).  Rounds only.
+    // carry chains run once for the M numbers (walk_sib).  Rounds, or with
+    // VD & 131072 the sibling parts on a persistent grid (SIBPERS: workgroup
+    // g of G walks the strided 64-unit batches g, g + G, ... of the sibling
+    // and edge units, its waves pulling them from an LDS counter; the
+    // remainder's regular parts stay rounds of the same launch, so PERS --
+    // the regular parts' grid -- stays off).
     static constexpr int SIB = SIB_;
+    static constexpr bool SIBPERS = SIB_ > 1 && (VD_ & 131072) != 0;
     static constexpr bool PERS = SIB_ > 1 ? false : PERS_ >= 0 ? PERS_ != 0 : (WG >= 1024 && one_wg_per_cu(BASE, WG));
+    // the persistent twin of a sibling rounds kernel, where one is built: the
+    // b40 pipelined walk on the ND = 4 layouts (plan_sib_pers decides per
+    // segment whether it runs)
+    using SibPers = Cfg<BASE_, ND_, NE_, NE2_, PROBE_, WG_, VD_ | 131072, LG_, PERS_, SIB_>;
+    static constexpr bool HAS_SIBPERS =
+        SIB_ > 1 && (VD_ & 131072) == 0 && PROBE_ == 0 && BASE_ == 40 && ND_ == 4 && LG >= 100;
     // the same kernel with rounds of workgroups (launch_cfg falls back to it
     // when the runtime occupancy or the field size does not suit PERS), at
     // the workgroup size rounds prefer
@@ -423,7 +435,7 @@ struct Cfg {
     static constexpr bool VDL = ((VD & 256) != 0 || NOTAB) && !LSD;
     static constexpr u32 MAGIC_D = (u32)(((1ull << 32) + ES * BASE - 1) / (ES * BASE));
     static_assert(VD == 0 || (MW >= 2 && split_exact(BASE, ES, MAGIC_D)), "VALU digit split");
-    static_assert(VDC <= NE + 1 - (MW <= 2 ? 1 : 0) && VDS <= ND + 1 && (VD & ~0x1ffff) == 0 &&
+    static_assert(VDC <= NE + 1 - (MW <= 2 ? 1 : 0) && VDS <= ND + 1 && (VD & ~0x3ffff) == 0 &&
                       ((VD & 1024) == 0 || LSDX),
                   "VALU-decoded limbs");
     // Waves per SIMD: what the LDS allows, capped by what the lane state

@@ -14,6 +14,7 @@ namespace fd2 {
 
 NICE_PROBE_ONLY(u64 *g_stamps = nullptr; u64 g_last_launch[6] = {};)  // phase stamps, last launch (probe build)
 std::atomic<uint32_t> g_force_sib_stride{0};  // nice_debug_force_sib_stride
+std::atomic<uint32_t> g_force_sib_pers[2] = {{0}, {0}};  // nice_debug_force_sib_persistent: mode, workgroup cap
 
 // ---------------------------------------------------------------------------
 // Host: limb counts per segment.  For a segment [a, e) the last FD state a
@@ -129,6 +130,10 @@ static hipError_t launch_segment(const DetailedLaunch &p, const Combo &c, int nu
 }  // namespace fd2
 
 void fd2_force_sib_stride(uint32_t L) { fd2::g_force_sib_stride.store(L, std::memory_order_relaxed); }
+void fd2_force_sib_persistent(uint32_t mode, uint32_t max_workgroups) {
+    fd2::g_force_sib_pers[1].store(max_workgroups, std::memory_order_relaxed);
+    fd2::g_force_sib_pers[0].store(mode, std::memory_order_relaxed);
+}
 
 bool fd2_supported(uint32_t base) {
     switch (base) {

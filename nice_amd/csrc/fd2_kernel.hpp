@@ -41,7 +41,10 @@
 //  * Grid: rounds of workgroups, one chunk per lane, where two or more
 //    workgroups share a CU (b40); one round of resident 1024-thread
 //    workgroups whose waves pull strided 64-unit batches where one workgroup
-//    fills a CU (Cfg::PERS, b42..80 fields of >= 2 rounds).
+//    fills a CU (Cfg::PERS, b42..80 fields of >= 2 rounds).  The b40 sibling
+//    kernel's pipelined fields of >= 4 batches per resident wave run their
+//    sibling parts on such a grid too (Cfg::SIBPERS, two 512-thread
+//    workgroups per CU; fd2_plan.hpp plan_sib_pers).
 //
 // The kernel is issue-bound on VALU and LDS together: b40 per n is 13 random
 // 8-byte LDS lookups (≈5 LDS cycles each per wave) and ≈78 VALU instructions
@@ -584,6 +587,16 @@ constexpr u32 kStampGroups = 65536, kStampWords = 32;
         }                                                                                        \
     } while (0)
 #define FD2_STAMP(a, k) FD2_STAMP_P((a).stamps, k)
+// The sibling parts stamp phases 14 (barrier passed) and 15 (thread 0's steps
+// done), and lane 0 of wave w < 8 the shader clock at the end of the wave's
+// steps into word 20 + w (the spread of a workgroup's wave finish times).
+#define FD2_WAVE_STAMP(a)                                                                        \
+    do {                                                                                         \
+        if (kProbes && (a).stamps && (threadIdx.x & 63) == 0 && threadIdx.x < 512 &&             \
+            blockIdx.x < kStampGroups)                                                           \
+            (a).stamps[kStampWords * (u64)blockIdx.x + 20 + (threadIdx.x >> 6)] =                \
+                __builtin_amdgcn_s_memtime();                                                    \
+    } while (0)
 
 struct Fd2Args {
     u64 *stamps;  // probe build: phase stamps (null in the product build)
@@ -1065,8 +1078,33 @@ struct SibUnit {
     u32 chunk;
     u64 lo, hi;
 };
+// Persistent sibling grid (Cfg::SIBPERS): the 64-unit batch each wave of the
+// workgroup is on, kept in LDS for the near-miss path (not live in a VGPR).
+template <class P>
+__device__ __forceinline__ u32 *sib_batch_slot() {
+    __shared__ u32 cur[P::WG / 64];
+    return &cur[threadIdx.x >> 6];
+}
+// ... and the unit of lane `lane` in batch b of the launch: batches [0, nsb)
+// hold the sibling units 64 b + lane, the batches after them the edge units.
+template <class P>
+__device__ __forceinline__ SibUnit sib_unit_at(const Fd2Args &a, u32 b, u32 lane) {
+    const u32 nsb = (a.sib_units + 63) / 64;
+    const bool edge = b >= nsb;
+    const u32 sunit = 64 * (edge ? b - nsb : b) + lane;
+    const u32 upb = edge ? 1u : a.sib_upb;
+    SibUnit u;
+    u.active = sunit < (edge ? a.edge_units : a.sib_units);
+    u.chunk = edge ? a.edge_chunk : a.sib_chunk;
+    const u32 q = sunit / upb, k = sunit - q * upb;
+    u.lo = edge ? a.edge_lo : a.sib_lo;
+    u.hi = edge ? a.edge_hi : a.sib_hi;
+    add_u128(u.lo, u.hi, (u64)q * ((u64)P::SIB * P::B * P::B) + (u64)k * u.chunk);
+    return u;
+}
 template <class P>
 __device__ __forceinline__ SibUnit sib_unit(const Fd2Args &a) {
+    if constexpr (P::SIBPERS) return sib_unit_at<P>(a, *sib_batch_slot<P>(), threadIdx.x & 63);
     const bool edge = blockIdx.x >= a.sib_blocks;
     const u32 sunit = (edge ? blockIdx.x - a.sib_blocks : blockIdx.x) * P::WG + threadIdx.x;
     const u32 upb = edge ? 1u : a.sib_upb;
@@ -1425,7 +1463,55 @@ __device__ __forceinline__ void fd2_body(const Fd2Args &a) {
     // regular path's (one State live at the barrier, not M + 1).
     bool sib_done = false;
     if constexpr (P::SIB > 1) {
-        if (sib_part) {
+        if constexpr (P::SIBPERS) {
+            // Persistent sibling grid: the a.sib_blocks workgroups of the
+            // sibling part are one round of resident ones.  Workgroup g owns
+            // the batches g + G k, k < nk, of the launch's sibling and edge
+            // batches (strided, as the regular persistent grid's); after the
+            // one barrier its waves take k = wave, then pull the next k from
+            // an LDS counter, until the batches run out or a wave has taken
+            // wave_cap of them (its lanes' u16 window counters hold
+            // wave_cap M L numbers; the host sizes launches so the waves'
+            // caps cover every workgroup's batches).  Every loop bound is the
+            // host's: no workgroup waits for another.
+            if (sib_part) {
+                __shared__ u32 sib_next;
+                const u32 G = a.sib_blocks;
+                const u32 nb = (a.sib_units + 63) / 64 + (a.edge_units + 63) / 64;
+                const u32 nk = nb > blockIdx.x ? (nb - blockIdx.x + G - 1) / G : 0;
+                if (tid == 0) sib_next = P::WG / 64;
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                FD2_STAMP(a, 14);
+                u32 k = __builtin_amdgcn_readfirstlane(tid >> 6), taken = 0;
+                while (k < nk) {
+                    const u32 b = blockIdx.x + G * k;
+                    if (lane_id == 0) *sib_batch_slot<P>() = b;
+                    const SibUnit su = sib_unit_at<P>(a, b, lane_id);
+                    if (su.active) {
+                        State<P> sst[P::SIB];
+                        u32 X[P::NX];
+                        init_digits<P>(X, su.lo, su.hi);
+                        init_plain<P>(sst[0], X);
+#pragma unroll
+                        for (int j = 1; j < P::SIB; j++) sib_derive<P>(sst[j], sst[0], X, (u32)j);
+#pragma unroll
+                        for (int j = 0; j < P::SIB; j++) {
+                            init_scale<P>(sst[j]);
+                            sib_park<P>(sst[j], j, smem);
+                        }
+                        walk_sib<P>(sst, smem, a, su.chunk, hbase, hinc, outl, cutoff, out);
+                    }
+                    if (++taken >= a.wave_cap) break;
+                    u32 next = 0;
+                    if (lane_id == 0) next = atomicAdd(&sib_next, 1u);
+                    k = __builtin_amdgcn_readfirstlane(__shfl(next, 0));
+                }
+                FD2_STAMP(a, 15);
+                FD2_WAVE_STAMP(a);
+                sib_done = true;
+            }
+        } else if (sib_part) {
             State<P> sst[P::SIB];
             const SibUnit su = sib_unit<P>(a);
             if (su.active) {
@@ -1442,7 +1528,10 @@ __device__ __forceinline__ void fd2_body(const Fd2Args &a) {
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
+            FD2_STAMP(a, 14);  // sibling part: state built, tables in LDS
             if (su.active) walk_sib<P>(sst, smem, a, su.chunk, hbase, hinc, outl, cutoff, out);
+            FD2_STAMP(a, 15);  // sibling part: thread 0's steps done
+            FD2_WAVE_STAMP(a);
             sib_done = true;
         }
     }

@@ -21,6 +21,9 @@ namespace fd2 {
 NICE_PROBE_ONLY(extern u64 *g_stamps; extern u64 g_last_launch[6];)  // last launch: grid, WG, chunk, nunits, tail, per_cu
 // Forced sibling lane stride (nice_debug_force_sib_stride; 0: the model's pick).
 extern std::atomic<uint32_t> g_force_sib_stride;
+// Forced persistent sibling grid (nice_debug_force_sib_persistent): [0] the
+// mode (0: production, 1: on, 2: never), [1] mode 1's workgroup cap (0: none).
+extern std::atomic<uint32_t> g_force_sib_pers[2];
 
 // The table image for this device and base, built on first use (the layout
 // depends on the base only) and kept for the process.
@@ -74,6 +77,8 @@ static PlanKnobs<P> fd2_knobs() {
     k.min_chunk = probe_knob("NICE_FD2_MINCHUNK", k.min_chunk);
     k.sib_chunk = probe_knob("NICE_FD2_SIBCHUNK", k.sib_chunk);
     k.sib_rounds = probe_knob("NICE_FD2_SIBROUNDS", k.sib_rounds);
+    k.sib_pers_min = probe_knob("NICE_FD2_SIBPERS_MIN", k.sib_pers_min);
+    k.sib_pers_k = probe_knob("NICE_FD2_SIBPERS_K", k.sib_pers_k);
     return k;
 }
 
@@ -108,6 +113,9 @@ static hipError_t fd2_enqueue(Fd2Args &a, const DetailedLaunch &q, const uint4 *
 
 template <class P>
 static hipError_t launch_sib(const DetailedLaunch &p, int num_cus, hipStream_t s);
+template <class K, class P>
+static hipError_t launch_sib_shape(const DetailedLaunch &p, const SibShape &sh, const uint4 *tabs,
+                                   const PlanKnobs<P> &knobs, int num_cus, int per_cu, hipStream_t s);
 
 template <class P>
 static hipError_t launch_cfg(const DetailedLaunch &p, int num_cus, hipStream_t s) {
@@ -180,21 +188,46 @@ static hipError_t launch_sib(const DetailedLaunch &p, int num_cus, hipStream_t s
     const uint4 *tabs = nullptr;
     hipError_t e = fd2_tables<P>(s, &tabs);
     if (e != hipSuccess) return e;
-    const PlanKnobs<P> knobs = fd2_knobs<P>();
+    PlanKnobs<P> knobs = fd2_knobs<P>();
+    if constexpr (P::HAS_SIBPERS) {
+        knobs.sib_pers_mode = g_force_sib_pers[0].load(std::memory_order_relaxed);
+        knobs.sib_pers_max_wg = g_force_sib_pers[1].load(std::memory_order_relaxed);
+    }
     const u128 seg_start = ((u128)p.start_hi << 64) | p.start_lo;
-    const SibShape sh = plan_sib<P>(seg_start, p.count, num_cus, per_cu, p.overlapped != 0,
-                                    g_force_sib_stride.load(std::memory_order_relaxed), knobs);
+    SibShape sh = plan_sib<P>(seg_start, p.count, num_cus, per_cu, p.overlapped != 0,
+                              g_force_sib_stride.load(std::memory_order_relaxed), knobs);
     if (sh.kind == SibShape::kNoSib) return launch_cfg<typename P::NoSib>(p, num_cus, s);
     if (sh.kind == SibShape::kError) return hipErrorInvalidValue;
     if (p.sib) {
         p.sib[0] = (uint32_t)P::SIB;
         p.sib[1] = (uint32_t)sh.L;
+        p.sib[2] = 0;
     }
+    // the persistent twin (same tables, same plan arithmetic) where the
+    // segment is long enough for it
+    if constexpr (P::HAS_SIBPERS) {
+        const int pq = fd2_occupancy<typename P::SibPers>();
+        if (pq >= 1) {
+            plan_sib_pers<P>(sh, p.count, num_cus, pq, p.overlapped != 0, knobs);
+            if (sh.pers) return launch_sib_shape<typename P::SibPers, P>(p, sh, tabs, knobs, num_cus, pq, s);
+        }
+    }
+    return launch_sib_shape<P, P>(p, sh, tabs, knobs, num_cus, per_cu, s);
+}
+
+// The launches of a sibling segment of shape sh with kernel K (P, or its
+// persistent twin P::SibPers when sh.pers).
+template <class K, class P>
+static hipError_t launch_sib_shape(const DetailedLaunch &p, const SibShape &sh, const uint4 *tabs,
+                                   const PlanKnobs<P> &knobs, int num_cus, int per_cu, hipStream_t s) {
+    static_assert(K::SIBPERS || std::is_same<K, P>::value, "the rounds kernel or its persistent twin");
     constexpr u64 SB = (u64)P::SIB * P::B * P::B;
+    hipError_t e;
     DetailedLaunch q = p;
     u64 left = p.count;
     while (left) {
         const SibLaunchPlan pl = plan_sib_launch<P>(left, sh, num_cus, per_cu, knobs);
+        if (K::SIBPERS && p.sib && pl.sib_blocks) p.sib[2] = (uint32_t)pl.sib_blocks;
         Fd2Args a{};
         a.sib_lo = a.edge_lo = q.start_lo;
         a.sib_hi = a.edge_hi = q.start_hi;
@@ -209,12 +242,12 @@ static hipError_t launch_sib(const DetailedLaunch &p, int num_cus, hipStream_t s
         u64 lo = q.start_lo, hi = q.start_hi;  // the remainder follows the super-blocks
         add_u128(lo, hi, pl.Q * SB);
         fd2_regular_parts(a, lo, hi, pl.nunits, pl.chunk, pl.tail, pl.main_blocks);
-        a.wave_cap = 0;
+        a.wave_cap = pl.wave_cap;
         NICE_PROBE_ONLY({
             const u64 v[6] = {pl.grid, (u64)P::WG, sh.L, pl.sib_units, pl.R, (u64)per_cu};
             for (int k = 0; k < 6; k++) g_last_launch[k] = v[k];
         })
-        if ((e = fd2_enqueue<P>(a, q, tabs, left == pl.cnt, pl.grid, s)) != hipSuccess) return e;
+        if ((e = fd2_enqueue<K>(a, q, tabs, left == pl.cnt, pl.grid, s)) != hipSuccess) return e;
         add_u128(q.start_lo, q.start_hi, pl.cnt);
         left -= pl.cnt;
     }

@@ -33,7 +33,9 @@ static hipError_t try_combo(const DetailedLaunch &p, int nd, int ne, int ne2, bo
         // sibling units): on the first limb layout (the range's first ~29 %,
         // the benchmark fields) pipelined with the lowest C limb above the
         // shared one decoded by VALU, elsewhere per-sibling lookup groups, no
-        // VALU decode (profiles/r05/sib_sweep_range.log)
+        // VALU decode (profiles/r05/sib_sweep_range.log).  The pipelined one
+        // has a persistent-grid twin (Cfg::SibPers), which launch_sib picks
+        // for long pipelined segments (plan_sib_pers)
         if constexpr (B_ == 40) {
             if (!wg512) {
                 if constexpr (ND_ == 4) return launch_cfg<Cfg<B_, ND_, NE_, NE2_, 0, 512, 4097, 100, 0, 3>>(p, num_cus, s);

@@ -221,6 +221,15 @@ struct PlanKnobs {
     u64 min_chunk = 4;
     u64 sib_chunk = 0;    // a sibling lane stride instead of the pickers' (0: none)
     u64 sib_rounds = 15;  // tenths of a round below which a small field leaves the sibling kernel
+    // Persistent sibling grid (Cfg::SIBPERS, plan_sib_pers): a segment takes
+    // it at or above sib_pers_min tenths of a wave batch per resident wave;
+    // the grid is sib_pers_k rounds of resident workgroups (1: one round).
+    u64 sib_pers_min = 40;
+    u64 sib_pers_k = 1;
+    // the test hook's (nice_debug_force_sib_persistent): mode 1 = on for every
+    // sibling segment, with at most sib_pers_max_wg workgroups when nonzero;
+    // mode 2 = never
+    u32 sib_pers_mode = 0, sib_pers_max_wg = 0;
 };
 
 // Rounds of one chunk per lane: `cnt` numbers over whole rounds of `lanes`
@@ -342,6 +351,10 @@ struct SibShape {
     u64 U, upb, r;  // units per B^2 block: upb full ones of L numbers, and the edge unit of r (when r != L)
     bool has_edge;
     u64 qmax;       // super-blocks per launch
+    // persistent sibling grid (plan_sib_pers; pers false: rounds)
+    bool pers;
+    u64 pers_grid;  // workgroups of a launch's sibling part, at most
+    u32 wave_cap;   // batches one wave may take: wave_cap M L <= 65535
 };
 // Too short for the sibling walk to pay (fewer than 4 super-blocks): the same
 // base without siblings.  The launcher asks this first, before it builds the
@@ -386,7 +399,8 @@ static SibShape plan_sib(u128 seg_start, u64 count, int num_cus, int per_cu, boo
         double rounds = 0;
         L = pick_small_stride<P>(seg_start, count, P::TCHUNK * 3 / 4, P::TCHUNK * 5 / 4, P::LO + 1, Q0, lanes, D,
                                  rounds);
-        if (10 * rounds < (double)k.sib_rounds) return sh;
+        // (the persistent grid forced on by the test hook keeps such a field)
+        if (10 * rounds < (double)k.sib_rounds && k.sib_pers_mode != 1) return sh;
     }
     // Target stride: TCHUNK, or 140 for the pipelined walk (LG >= 100), which
     // fills and drains its lookup pipeline once per unit and so gains from
@@ -441,17 +455,77 @@ struct SibLaunchPlan {
     u64 Q, cnt, R;
     u64 chunk, nunits, tail;  // the remainder's parts
     u64 sib_units, sib_blocks, edge_units, edge_blocks, main_blocks, grid;
+    // persistent sibling grid (sh.pers): the launch's 64-unit batches (the
+    // sibling units', then the edge units'), walked by sib_blocks workgroups
+    // whose waves take at most wave_cap each; edge_blocks is 0
+    u64 batches;
+    u32 wave_cap;
 };
+
+// Whether a sibling segment takes the persistent grid (Cfg::SIBPERS), and its
+// shape: sets sh.pers, sh.pers_grid, sh.wave_cap.  One round of resident
+// workgroups (k.sib_pers_k rounds: each workgroup then lives 1 / k of the
+// field, which lets another stream's launch in sooner); a wave stops after
+// wave_cap batches, so its lanes' u16 window counters, which count M L
+// numbers per unit, cannot overflow.  A launch takes as many super-blocks as
+// the grid's caps cover (plan_sib_launch).
+//
+// Production takes it for a field that overlaps another (pipelined submits)
+// with at least k.sib_pers_min / 10 batches per resident wave.  In rounds a
+// workgroup's eight waves finish far apart -- the b40 1e9 field's wave 0 waits
+// 21 % of its workgroup's life at the end-of-walk barrier -- and the CU's
+// slot refills only when the last is done; on the persistent grid a wave that
+// finishes a batch starts the next.  Pipelined, b40 at the range start,
+// rounds -> persistent per step: 1e9 (8.9 batches per resident wave) 1.865 ->
+// 1.818 ms, 5e8 (4.4) 0.930 -> 0.915, 2.5e8 (2.2) 0.4712 -> 0.4709, so the
+// threshold sits at 4.  A lone field loses: nothing fills the CUs while the
+// one round of workgroups drains its last batches (1e9 kernel 1.882 -> 1.970
+// ms, 5e8 0.950 -> 0.967), so it keeps rounds and its whole-rounds stride.
+// Grids of 2 and 4 rounds of shorter-lived workgroups, which would let the
+// niceonly stream's launches in sooner, measured slower than one (bench step
+// 1.835 / 1.868 / 1.883 ms at k = 1 / 2 / 4 against 1.879 in rounds;
+// profiles/sib_persistent/).
+template <class P>
+static void plan_sib_pers(SibShape &sh, u64 count, int num_cus, int per_cu, bool overlapped,
+                          const PlanKnobs<P> &k = PlanKnobs<P>{}) {
+    constexpr u64 SB = (u64)P::SIB * P::B * P::B, NW = P::WG / 64;
+    sh.pers = false;
+    sh.pers_grid = 0;
+    sh.wave_cap = 0;
+    if (sh.kind != SibShape::kSib || k.sib_pers_mode == 2) return;
+    const u64 resident = (u64)num_cus * per_cu, Q = count / SB;
+    const u64 nb = (Q * sh.upb + 63) / 64 + (sh.has_edge ? (Q + 63) / 64 : 0);
+    if (k.sib_pers_mode != 1 && (!overlapped || 10 * nb < k.sib_pers_min * resident * NW)) return;
+    u64 G = resident * std::max<u64>(1, k.sib_pers_k);
+    if (k.sib_pers_mode == 1 && k.sib_pers_max_wg) G = std::min<u64>(G, k.sib_pers_max_wg);
+    const u64 cap = 65535 / ((u64)P::SIB * sh.L);
+    // not even one super-block's batches under the grid's caps: rounds
+    if (cap < 1 || (sh.upb + 63) / 64 + 1 > G * NW * cap) return;
+    sh.pers = true;
+    sh.pers_grid = G;
+    sh.wave_cap = (u32)cap;
+}
+
 template <class P>
 static SibLaunchPlan plan_sib_launch(u64 left, const SibShape &sh, int num_cus, int per_cu,
                                      const PlanKnobs<P> &k = PlanKnobs<P>{}) {
-    constexpr u64 SB = (u64)P::SIB * P::B * P::B, LMAX = (u64)P::LDE - P::B;
+    constexpr u64 SB = (u64)P::SIB * P::B * P::B, LMAX = (u64)P::LDE - P::B, NW = P::WG / 64;
     const u64 lanes = (u64)num_cus * per_cu * P::WG;
     SibLaunchPlan pl{};
     pl.Q = left / SB;
     pl.cnt = left;
-    if (pl.Q > sh.qmax) {
-        pl.Q = sh.qmax;
+    u64 qmax = sh.qmax;
+    if (sh.pers) {
+        // Q super-blocks are at most Q (upb + 1) / 64 + 2 batches; workgroup g
+        // takes every pers_grid-th, so the launch fits while its batches are at
+        // most pers_grid NW wave_cap.  (64 b + lane stays in 32 bits.)
+        const u64 room = sh.pers_grid * NW * sh.wave_cap;
+        const u64 per = sh.upb + (sh.has_edge ? 1 : 0);
+        qmax = std::min<u64>(qmax, std::max<u64>(1, room > 2 ? (room - 2) * 64 / per : 0));
+        qmax = std::min<u64>(qmax, std::max<u64>(1, 0xffffffc0ull / sh.upb));
+    }
+    if (pl.Q > qmax) {
+        pl.Q = qmax;
         pl.cnt = pl.Q * SB;
     }
     pl.R = pl.cnt - pl.Q * SB;
@@ -465,6 +539,12 @@ static SibLaunchPlan plan_sib_launch(u64 left, const SibShape &sh, int num_cus, 
     pl.sib_blocks = (pl.sib_units + P::WG - 1) / P::WG;
     pl.edge_units = sh.has_edge ? pl.Q : 0;
     pl.edge_blocks = (pl.edge_units + P::WG - 1) / P::WG;
+    if (sh.pers) {
+        pl.batches = (pl.sib_units + 63) / 64 + (pl.edge_units + 63) / 64;
+        pl.sib_blocks = std::min<u64>(sh.pers_grid, (pl.batches + NW - 1) / NW);
+        pl.edge_blocks = 0;
+        pl.wave_cap = sh.wave_cap;
+    }
     pl.main_blocks = (pl.nunits + P::WG - 1) / P::WG;
     pl.grid = pl.sib_blocks + pl.edge_blocks + pl.main_blocks + (pl.tail + P::WG - 1) / P::WG;
     return pl;

@@ -51,7 +51,8 @@ struct DetailedLaunch {
     FieldFinish fin;             // fd2 only; see FieldFinish
     uint32_t *launches;          // if set, incremented per kernel launch enqueued
     uint32_t *sib;               // fd2, if set: [0] sibling lanes M of the field's last sibling-lane
-                                 // launch (0: none ran), [1] its lane stride L
+                                 // launch (0: none ran), [1] its lane stride L, [2] the workgroups of
+                                 // its persistent sibling grid (0: rounds)
     uint32_t overlapped;         // fd2: another field of the device was still running when this one
                                  // was enqueued (the pipelined case), so launches are shaped for
                                  // throughput, not for the latency of a lone field
@@ -98,6 +99,10 @@ hipError_t launch_detailed_fd2_batch(const BatchLaunch &p, hipStream_t s);
 // Test hook: every later sibling-lane launch of the process uses lane stride
 // L (odd; 0 restores the production pick, fd2_plan.hpp plan_sib).
 void fd2_force_sib_stride(uint32_t L);
+// Test hook: the persistent sibling grid (fd2_plan.hpp plan_sib_pers) of every
+// later sibling-lane launch: mode 0 production, 1 on for every sibling
+// segment (at most max_workgroups workgroups when nonzero), 2 never.
+void fd2_force_sib_persistent(uint32_t mode, uint32_t max_workgroups);
 // The base's compile-time histogram window [w0, w0 + w) (fd2_cfg.hpp
 // window_w0 / window_w); false for a base without an FD kernel.  The FD
 // launchers accept a cutoff with cutoff + 1 >= w0 + w.
