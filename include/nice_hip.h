@@ -449,6 +449,73 @@ int nice_cpu_process_ranges_detailed(uint32_t base, const uint64_t *bounds, size
 int nice_debug_ranges_plan(uint32_t base, const uint64_t *bounds, size_t n_ranges,
                            uint64_t *units, size_t cap, size_t *n_out);
 
+/* Batched niceonly ranges: the niceonly twin of nice_process_ranges_detailed,
+ * and the seam for a caller that keeps its own MSD producer (the reference's
+ * GPU pipeline hands its kernel only the surviving ranges,
+ * client_process_gpu.rs:589-796).  `bounds` holds four u64 per range --
+ * start_lo, start_hi, end_lo, end_hi, the layout nice_msd_valid_ranges writes,
+ * so its output can be passed straight in.
+ * No MSD filter runs on a range: every stride candidate of every range -- the
+ * (b - 1) * b^k table with k = stride_k, 0 meaning 2 -- gets the full test,
+ * which is the contract of the reference's niceonly_ranges_kernel
+ * (nice_kernels.cu:420-470): the caller did the filtering.  So there is no
+ * filter option; Filter C and the sound prefix test belong to the MSD recursion.
+ *   candidates[i] (may be null): the stride candidates in range i.
+ *   square_ok[i] (may be null): how many of them have a repeat-free square,
+ *     counted where the field path counts it -- a nice_niceonly_fast_base, the
+ *     range wholly inside the base's valid range, k = 2 -- and 0 elsewhere.
+ * Those ranges run the base's compile-time kernel and are counted in
+ * nice_ranges_niceonly_stats.fast_ranges; every other range runs the
+ * run-time-base test (generic_ranges).  Each group's leaves are dealt to the
+ * context's devices in contiguous runs balanced by candidates: at most two
+ * launches per device.
+ * The list is the concatenation, in range order, of each range's passing
+ * numbers in ascending order; out_range[j] (may be null) is entry j's range
+ * index; num_uniques is the base, as in every niceonly entry.  Ranges may
+ * overlap or repeat: each gets its own complete answer, so a number inside two
+ * ranges is listed twice.  nice_debug_set_nice_min applies exactly as it does
+ * to a field submitted at that moment (the fast ranges list union counts >=
+ * nice_min).  A residue-empty base returns all-zero counts and an empty list
+ * with no launch.
+ * Errors: NICE_ERR_INVALID (n_ranges 0 or above 2^20; an empty or inverted
+ * range -- the message names its index --; a range holding more than 2^40
+ * candidates, or a call of more than 2^24 leaf records: use a field instead;
+ * a stride modulus above u32; a base outside 2..128), NICE_ERR_CAPACITY
+ * (*n_out = the needed length; the results are kept, and the same call with
+ * room returns them without running again).
+ * The call has its own stream, buffers and lock per device: it takes no
+ * niceonly slot and does not wait for fields in flight. */
+int nice_process_ranges_niceonly(nice_ctx *ctx, uint32_t base, const uint64_t *bounds,
+                                 size_t n_ranges, uint32_t stride_k, uint64_t *candidates,
+                                 uint32_t *square_ok, nice_number *out, uint32_t *out_range,
+                                 size_t cap, size_t *n_out);
+typedef struct {
+    uint32_t launches;       /* kernel launches of the last call that ran (a retry after
+                                NICE_ERR_CAPACITY returns kept results and leaves the statistics) */
+    uint32_t fast_ranges;    /* ranges run by the base's compile-time kernel (square_ok counted) */
+    uint32_t generic_ranges; /* ranges run by the run-time-base test */
+    uint32_t reserved;
+    uint64_t candidates;     /* summed over the ranges */
+    uint64_t square_ok;
+    double kernel_ms;        /* HIP events around the launches (the slowest device) */
+} nice_ranges_niceonly_stats;
+int nice_last_ranges_niceonly_stats(nice_ctx *ctx, nice_ranges_niceonly_stats *out);
+/* The same on the host cores (no device): the stride walk of
+ * stride_filter.rs:139-155 over each range with get_is_nice, the ranges spread
+ * over `threads`.  square_ok is counted for every range. */
+int nice_cpu_process_ranges_niceonly(uint32_t base, const uint64_t *bounds, size_t n_ranges,
+                                     uint32_t stride_k, int32_t threads, uint64_t *candidates,
+                                     uint32_t *square_ok, nice_number *out, uint32_t *out_range,
+                                     size_t cap, size_t *n_out);
+/* Test hook (no device): the leaf plan of nice_process_ranges_niceonly on a
+ * context of n_devices devices.  Writes 7 u64 per leaf: b0_lo, b0_hi (the
+ * cycle base start - start mod M), g0, count, range index, group (1: fast, 0:
+ * generic), device.  Leaves of the fast group first, each group in range
+ * order.  *n_out = the true count. */
+int nice_debug_ranges_niceonly_plan(uint32_t base, uint32_t stride_k, const uint64_t *bounds,
+                                    size_t n_ranges, uint32_t n_devices, uint64_t *leaves,
+                                    size_t cap, size_t *n_out);
+
 /* Diagnostics: per-n results of the device functions the kernels use. */
 int nice_debug_unique_counts(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t count,
                              uint32_t base, uint32_t *out);

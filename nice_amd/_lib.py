@@ -51,6 +51,8 @@ EXPORTS = (
     "nice_process_ranges_detailed", "nice_last_ranges_stats", "nice_cpu_process_ranges_detailed",
     "nice_debug_ranges_plan", "nice_debug_set_near_miss_cutoff", "nice_debug_fd_window",
     "nice_debug_set_nice_min", "nice_debug_cube_count", "nice_debug_force_sib_persistent",
+    "nice_process_ranges_niceonly", "nice_last_ranges_niceonly_stats", "nice_cpu_process_ranges_niceonly",
+    "nice_debug_ranges_niceonly_plan",
 )
 
 
@@ -94,6 +96,13 @@ class nice_kernel_stats(ctypes.Structure):
 class nice_ranges_stats(ctypes.Structure):
     _fields_ = [("launches", ctypes.c_uint32), ("fallback_ranges", ctypes.c_uint32),
                 ("numbers", ctypes.c_uint64), ("kernel_ms", ctypes.c_double)]
+
+
+class nice_ranges_niceonly_stats(ctypes.Structure):
+    _fields_ = [("launches", ctypes.c_uint32), ("fast_ranges", ctypes.c_uint32),
+                ("generic_ranges", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("candidates", ctypes.c_uint64), ("square_ok", ctypes.c_uint64),
+                ("kernel_ms", ctypes.c_double)]
 
 
 _lib = None
@@ -178,6 +187,10 @@ def lib():
         "nice_last_ranges_stats": ([vp, ctypes.POINTER(nice_ranges_stats)], i32),
         "nice_cpu_process_ranges_detailed": ([u32, P64, sz, u32, i32, P64, PN, P32, sz, PSZ], i32),
         "nice_debug_ranges_plan": ([u32, P64, sz, P64, sz, PSZ], i32),
+        "nice_process_ranges_niceonly": ([vp, u32, P64, sz, u32, P64, P32, PN, P32, sz, PSZ], i32),
+        "nice_last_ranges_niceonly_stats": ([vp, ctypes.POINTER(nice_ranges_niceonly_stats)], i32),
+        "nice_cpu_process_ranges_niceonly": ([u32, P64, sz, u32, i32, P64, P32, PN, P32, sz, PSZ], i32),
+        "nice_debug_ranges_niceonly_plan": ([u32, u32, P64, sz, u32, P64, sz, PSZ], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

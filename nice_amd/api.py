@@ -184,6 +184,16 @@ class RangesStats:
     kernel_ms: float      # HIP events around the batch launches
 
 
+@dataclass
+class RangesNiceonlyStats:
+    launches: int        # kernel launches of the call (at most two per device)
+    fast_ranges: int     # ranges run by the base's compile-time kernel (square_ok counted)
+    generic_ranges: int  # ranges run by the run-time-base test
+    candidates: int      # summed over the ranges
+    square_ok: int
+    kernel_ms: float     # HIP events around the launches (the slowest device)
+
+
 def _pack_ranges(ranges):
     """(start, end) pairs or FieldSize -> the four-u64-per-range bounds array
     nice_msd_valid_ranges writes."""
@@ -191,9 +201,15 @@ def _pack_ranges(ranges):
              for r in ranges]
     if any(s < 0 or e < 0 or s >> 128 or e >> 128 for s, e in pairs):
         raise ValueError("value must fit in u128")
-    flat = array.array("Q", [x for s, e in pairs for x in (s & MASK64, s >> 64, e & MASK64, e >> 64)])
     if not pairs:
         flat = array.array("Q", [0, 0, 0, 0])
+    elif max(e for _, e in pairs) <= MASK64 and max(s for s, _ in pairs) <= MASK64:
+        # (hundreds of thousands of survey windows: strided copies instead of a Python loop per value)
+        flat = array.array("Q", bytes(32 * len(pairs)))
+        flat[0::4] = array.array("Q", [s for s, _ in pairs])
+        flat[2::4] = array.array("Q", [e for _, e in pairs])
+    else:
+        flat = array.array("Q", [x for s, e in pairs for x in (s & MASK64, s >> 64, e & MASK64, e >> 64)])
     # (one buffer copy: filling a ctypes array element by element costs ~1 us per value)
     return (ctypes.c_uint64 * len(flat)).from_buffer_copy(flat), len(pairs)
 
@@ -331,6 +347,28 @@ class GpuContext:
         s = _lib.nice_ranges_stats()
         check(lib().nice_last_ranges_stats(self._h, s))
         return RangesStats(s.launches, s.fallback_ranges, s.numbers, s.kernel_ms)
+
+    # -- batched niceonly ranges ------------------------------------------------
+    def niceonly_ranges(self, ranges, base: int, stride_k: int = 0, cap: int = 0):
+        """Many ranges in one call (nice_process_ranges_niceonly): `ranges`
+        holds (start, end) pairs or FieldSize, e.g. what get_valid_ranges
+        returns.  No MSD filter runs: every stride candidate of every range is
+        tested.  Returns (candidates, square_ok, [(n, range_index)]): per range
+        its stride candidates and how many have a repeat-free square (counted
+        for a niceonly fast base's ranges inside its valid range on the k = 2
+        table, else 0), and each range's nice numbers ascending, in range
+        order.  See ranges_niceonly_stats()."""
+        bounds, n_ranges = _pack_ranges(ranges)
+        return _niceonly_ranges_call(
+            lambda *a: lib().nice_process_ranges_niceonly(self._h, base, bounds, n_ranges, stride_k, *a),
+            n_ranges, cap)
+
+    def ranges_niceonly_stats(self) -> "RangesNiceonlyStats":
+        """Statistics of this context's last niceonly_ranges call."""
+        s = _lib.nice_ranges_niceonly_stats()
+        check(lib().nice_last_ranges_niceonly_stats(self._h, s))
+        return RangesNiceonlyStats(s.launches, s.fast_ranges, s.generic_ranges, s.candidates, s.square_ok,
+                                   s.kernel_ms)
 
     # -- niceonly -------------------------------------------------------------
     def niceonly_raw(self, start: int, end: int, base: int, msd_floor: int = 0,
@@ -631,6 +669,54 @@ def process_ranges_detailed_gpu(ctx: GpuContext, ranges, base: int) -> List[Fiel
 def process_ranges_detailed_cpu(ranges, base: int, threads: int = 1) -> List[FieldResults]:
     """process_range_detailed_cpu for every range of `ranges`."""
     return _ranges_field_results(*detailed_ranges_cpu(ranges, base, threads=threads), base)
+
+
+def _niceonly_ranges_call(call, n_ranges: int, cap: int):
+    """call(candidates, square_ok, out, out_range, cap, n_out) -> rc, retried
+    with room on NICE_ERR_CAPACITY."""
+    cand = (ctypes.c_uint64 * max(n_ranges, 1))()
+    sq = (ctypes.c_uint32 * max(n_ranges, 1))()
+    cap = max(cap, 1024)
+    while True:
+        out, idx, n = _cpu_out(cap), (ctypes.c_uint32 * cap)(), ctypes.c_size_t()
+        rc = call(cand, sq, out, idx, cap, n)
+        if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
+            cap = n.value
+            continue
+        check(rc)
+        return (list(cand[:n_ranges]), list(sq[:n_ranges]),
+                [(out[i].number_lo | (out[i].number_hi << 64), idx[i]) for i in range(n.value)])
+
+
+def niceonly_ranges_cpu(ranges, base: int, stride_k: int = 0, threads: int = 1, cap: int = 0):
+    """GpuContext.niceonly_ranges on the host cores
+    (nice_cpu_process_ranges_niceonly): no device.  square_ok is counted for
+    every range."""
+    bounds, n_ranges = _pack_ranges(ranges)
+    return _niceonly_ranges_call(
+        lambda *a: lib().nice_cpu_process_ranges_niceonly(base, bounds, n_ranges, stride_k, threads, *a),
+        n_ranges, cap)
+
+
+def _ranges_niceonly_results(cand, lst, base: int) -> List[FieldResults]:
+    per = [[] for _ in cand]
+    for n, i in lst:
+        per[i].append(NiceNumberSimple(n, base))
+    return [FieldResults(distribution=[], nice_numbers=nn) for nn in per]
+
+
+def process_ranges_niceonly_gpu(ctx: GpuContext, ranges, base: int, stride_k: int = 0) -> List[FieldResults]:
+    """One FieldResults per range of `ranges`, from one batched call
+    (GpuContext.niceonly_ranges): the ranges are tested as given, with no MSD
+    filter in front."""
+    cand, _, lst = ctx.niceonly_ranges(ranges, base, stride_k)
+    return _ranges_niceonly_results(cand, lst, base)
+
+
+def process_ranges_niceonly_cpu(ranges, base: int, stride_k: int = 0, threads: int = 1) -> List[FieldResults]:
+    """process_ranges_niceonly_gpu on the host cores."""
+    cand, _, lst = niceonly_ranges_cpu(ranges, base, stride_k, threads)
+    return _ranges_niceonly_results(cand, lst, base)
 
 
 def process_range_niceonly_cpu(range_: FieldSize, base: int,

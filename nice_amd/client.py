@@ -20,6 +20,7 @@ merged in chunk order (compile_results).  No GPU is touched in that mode.
     python -m nice_amd detailed --benchmark extra-large --gpu
     python -m nice_amd --benchmark base-ten            # CPU mode
     python -m nice_amd --survey --base 50 --gpu        # distribution of a sampled base range
+    python -m nice_amd --survey-niceonly --base 50 --gpu   # what a niceonly search of the base would cost
 """
 from __future__ import annotations
 
@@ -76,10 +77,19 @@ def parse_args(argv=None):
     p.add_argument("--survey", action="store_true",
                    help="survey --base: the unique-digit distribution of a stratified sample of its "
                         "valid range in one batched call (nice_amd/survey.py); with --gpu on the GPU")
-    p.add_argument("--windows", type=int, default=4096, help="--survey: sample windows (strata)")
-    p.add_argument("--window-size", type=int, default=100_000, help="--survey: numbers per window")
-    p.add_argument("--seed", type=int, default=0, help="--survey: seed of the window offsets")
-    return p.parse_args(argv)
+    p.add_argument("--survey-niceonly", action="store_true",
+                   help="survey --base for a niceonly search: MSD survival, stride candidates, square survivors "
+                        "and numbers found in the same stratified windows, under the reference and the sound "
+                        "filter (nice_amd/survey.py survey_niceonly_base); with --gpu on the GPU; --msd-floor "
+                        "as a number (0 = 250)")
+    p.add_argument("--windows", type=int, default=4096, help="--survey, --survey-niceonly: sample windows (strata)")
+    p.add_argument("--window-size", type=int, default=None,
+                   help="numbers per window (--survey: 100000, --survey-niceonly: 1000000)")
+    p.add_argument("--seed", type=int, default=0, help="--survey, --survey-niceonly: seed of the window offsets")
+    args = p.parse_args(argv)
+    if args.window_size is None:
+        args.window_size = 100_000 if args.survey or not args.survey_niceonly else 1_000_000
+    return args
 
 
 def _devices(spec: str):
@@ -208,6 +218,30 @@ def run_survey(args, ctx) -> int:
     return 0
 
 
+def run_survey_niceonly(args, ctx) -> int:
+    """--survey-niceonly: print the niceonly survey of --base as one JSON line."""
+    from .survey import survey_niceonly_base
+    if not args.base:
+        log.error("--survey-niceonly needs --base")
+        return 2
+    if args.msd_floor == "adaptive":
+        log.error("--survey-niceonly needs a numeric --msd-floor")
+        return 2
+    floor = args.msd_floor or 250
+    t0 = time.perf_counter()
+    r = survey_niceonly_base(ctx, args.base, args.windows, args.window_size, args.seed, floor,
+                             threads=max(1, args.threads))
+    elapsed = time.perf_counter() - t0
+    log.info("✓ Surveyed %.2e numbers of base %d for niceonly in %.2fs", r.sampled, args.base, elapsed)
+    out = {"base": r.base, "windows": len(r.windows), "window_size": args.window_size, "seed": args.seed,
+           "msd_floor": floor, "range_size": str(r.range_size), "sampled": r.sampled}
+    for which in ("reference", "sound"):
+        f = getattr(r, which)
+        out[which] = dict(f.counts(), numbers_found=[str(n) for n in f.found], scaled=r.scaled(which))
+    print(json.dumps(out))
+    return 0
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     level = {"off": logging.CRITICAL + 10, "error": logging.ERROR, "warn": logging.WARNING,
@@ -225,6 +259,8 @@ def main(argv=None) -> int:
         log.info("CPU mode: %d threads", args.threads)
     if args.survey:
         return run_survey(args, ctx)
+    if args.survey_niceonly:
+        return run_survey_niceonly(args, ctx)
     while True:
         rc = run_once(args, ctx)
         if rc or not args.repeat:

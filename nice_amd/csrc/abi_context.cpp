@@ -220,6 +220,8 @@ void nice_ctx_destroy(nice_ctx *ctx) {
     if (!ctx) return;
     for (size_t i = 0; i < ctx->ranges.dev.size() && i < ctx->devs.size(); i++)
         ranges_dev_free(ctx->devs[i], ctx->ranges.dev[i]);
+    for (size_t i = 0; i < ctx->ranges_nice.dev.size() && i < ctx->devs.size(); i++)
+        ranges_nice_dev_free(ctx->devs[i], ctx->ranges_nice.dev[i]);
     for (auto &d : ctx->devs) device_free(d);
     delete ctx;
 }

@@ -20,6 +20,7 @@
 //   abi_detailed.cpp   detailed fields: enqueue, wait, gather + self-check
 //   abi_niceonly.cpp   niceonly fields: device MSD or host MSD producer
 //   abi_ranges.cpp     batched detailed ranges
+//   abi_ranges_niceonly.cpp  batched niceonly ranges
 //   abi_hooks.cpp      debug and check hooks
 //   host_parallel.cpp  host thread count and the adaptive MSD floor (no HIP)
 #pragma once
@@ -223,12 +224,41 @@ struct RangesState {
     std::vector<uint32_t> list_range;
 };
 
+// nice_process_ranges_niceonly: likewise one stream and its buffers per
+// device, apart from the niceonly slots -- its own copies of the residue
+// tables included (Device::residues belongs to fields, under ctx->mu) -- and
+// the last call's results while the caller retries with a longer list.
+struct RangesNiceDev {
+    hipStream_t stream = nullptr;
+    RangeLeaf *h_leaves = nullptr, *d_leaves = nullptr;  // pinned / device leaf records
+    size_t leaf_cap = 0;
+    uint32_t *d_sq = nullptr;  // square_ok, one counter per range
+    size_t sq_cap = 0;
+    uint32_t *d_ctl = nullptr;  // [0] the list count, then kDoneWords arrival counters
+    uint32_t *h_count = nullptr, *d_count_mapped = nullptr;  // mapped: the list count at a launch's end
+    ListBuf list;               // list.u: the entries' range indices
+    std::map<uint32_t, uint32_t *> residues;  // base*8+k -> device residue table
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+struct RangesNiceState {
+    std::vector<RangesNiceDev> dev;
+    nice_ranges_niceonly_stats stats{};
+    // kept after NICE_ERR_CAPACITY, for the same call with room
+    bool kept = false;
+    uint32_t base = 0, k = 0, nice_min = 0;
+    std::vector<uint64_t> bounds, candidates;
+    std::vector<uint32_t> square_ok;
+    std::vector<Entry> list;  // Entry::u: the range index
+};
+
 }  // namespace abi
 }  // namespace nice
 
 struct nice_ctx {
     std::mutex ranges_mu;  // serialises nice_process_ranges_detailed (not ctx->mu: fields in flight go on)
     nice::abi::RangesState ranges;
+    std::mutex ranges_nice_mu;  // ... and nice_process_ranges_niceonly
+    nice::abi::RangesNiceState ranges_nice;
     std::vector<nice::abi::Device> devs;
     std::mutex mu;  // serialises calls on one context (client_process_gpu.rs:196-201)
     std::condition_variable freed;  // a collect released a slot (synchronous submits wait on it)
@@ -469,6 +499,8 @@ int resolve_stats(Device &d);
 
 // abi_ranges.cpp: a device's batch stream and buffers (nice_ctx_destroy).
 void ranges_dev_free(Device &d, RangesDev &r);
+// abi_ranges_niceonly.cpp: likewise.
+void ranges_nice_dev_free(Device &d, RangesNiceDev &r);
 
 }  // namespace abi
 }  // namespace nice

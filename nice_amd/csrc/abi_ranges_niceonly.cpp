@@ -1,0 +1,300 @@
+// abi_ranges_niceonly.cpp -- batched niceonly ranges
+// (nice_process_ranges_niceonly): the caller's ranges, tested as given, in at
+// most two launches per device -- the base's compile-time kernel for the
+// ranges inside its valid range, the run-time-base kernel for the rest.  The
+// plan is niceonly_ranges_plan.hpp's, the kernel niceonly_ranges.hpp's.
+#include <cstring>
+
+#include "abi_internal.hpp"
+#include "niceonly_ranges_plan.hpp"
+
+using namespace nice::abi;
+using nice::u128;
+
+namespace {
+
+// A device's share of a call: its leaves, the fast group's first.
+struct DevShare {
+    std::vector<nice::RangeLeaf> leaves;
+    uint32_t n_fast = 0;
+};
+
+int ranges_nice_dev_init(Device &d, RangesNiceDev &r) {
+    if (r.stream) return NICE_OK;
+    HIPCHK(hipSetDevice(d.id));
+    HIPCHK(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreate(&r.ev0));
+    HIPCHK(hipEventCreate(&r.ev1));
+    HIPCHK(hipMalloc(&r.d_ctl, (1 + nice::kDoneWords) * 4));
+    HIPCHK(hipHostMalloc(&r.h_count, 4, hipHostMallocMapped | hipHostMallocCoherent));
+    *r.h_count = 0;
+    HIPCHK(hipHostGetDevicePointer((void **)&r.d_count_mapped, r.h_count, 0));
+    return NICE_OK;
+}
+
+}  // namespace
+
+void nice::abi::ranges_nice_dev_free(Device &d, RangesNiceDev &r) {
+    if (!r.stream) return;
+    (void)hipSetDevice(d.id);
+    (void)hipStreamSynchronize(r.stream);
+    if (r.h_leaves) (void)hipHostFree(r.h_leaves);
+    if (r.d_leaves) (void)hipFree(r.d_leaves);
+    if (r.d_sq) (void)hipFree(r.d_sq);
+    if (r.d_ctl) (void)hipFree(r.d_ctl);
+    if (r.h_count) (void)hipHostFree(r.h_count);
+    if (r.list.n) (void)hipFree(r.list.n);
+    if (r.list.u) (void)hipFree(r.list.u);
+    for (auto &kv : r.residues) (void)hipFree(kv.second);
+    if (r.ev0) (void)hipEventDestroy(r.ev0);
+    if (r.ev1) (void)hipEventDestroy(r.ev1);
+    (void)hipStreamDestroy(r.stream);
+}
+
+namespace {
+
+// What a call runs with, resolved once.
+struct NiceRangesCall {
+    uint32_t base, k, nice_min;
+    size_t n_ranges;
+    std::shared_ptr<nice::StrideTable> table;
+};
+
+// Enqueue a device's share (async on its batch stream): the leaves, the
+// counters zeroed, one launch per group present.
+int ranges_nice_enqueue(Device &d, RangesNiceDev &r, const NiceRangesCall &c, const DevShare &sh,
+                        uint32_t *launches) {
+    HIPCHK(hipSetDevice(d.id));
+    const uint32_t key = c.base * 8 + c.k;
+    if (!r.residues.count(key)) {
+        uint32_t *p = nullptr;
+        HIPCHK(hipMalloc(&p, c.table->residues.size() * 4));
+        r.residues[key] = p;
+        HIPCHK(hipMemcpy(p, c.table->residues.data(), c.table->residues.size() * 4, hipMemcpyHostToDevice));
+    }
+    const size_t nl = sh.leaves.size();
+    if (r.leaf_cap < nl) {
+        const size_t cap = std::max<size_t>(nl, 4096);
+        if (int rc = grow_pinned(r.h_leaves, r.leaf_cap, cap, cap * sizeof(nice::RangeLeaf))) return rc;
+        if (int rc = grow_device(r.d_leaves, r.leaf_cap, cap, cap * sizeof(nice::RangeLeaf))) return rc;
+    }
+    if (r.sq_cap < c.n_ranges) {
+        const size_t cap = std::max<size_t>(c.n_ranges, 1024);
+        if (int rc = grow_device(r.d_sq, r.sq_cap, cap, cap * 4)) return rc;
+    }
+    if (int rc = ensure_listbuf(d, r.list, std::max<uint32_t>(r.list.cap, 4096), true)) return rc;
+    std::memcpy(r.h_leaves, sh.leaves.data(), nl * sizeof(nice::RangeLeaf));
+    HIPCHK(hipMemcpyAsync(r.d_leaves, r.h_leaves, nl * sizeof(nice::RangeLeaf), hipMemcpyHostToDevice, r.stream));
+    HIPCHK(hipMemsetAsync(r.d_sq, 0, c.n_ranges * 4, r.stream));
+    HIPCHK(hipMemsetAsync(r.d_ctl, 0, (1 + nice::kDoneWords) * 4, r.stream));
+    *r.h_count = 0;
+    nice::NiceRangesLaunch p{};
+    p.c.residues = r.residues[key];
+    p.c.R = (uint32_t)c.table->residues.size();
+    p.c.M = (uint32_t)c.table->modulus;
+    p.c.base = c.base;
+    p.c.out = nice::NumOut{r.list.n, r.list.u, r.d_ctl, r.list.cap};
+    p.square_ok = r.d_sq;
+    p.done = r.d_ctl + 1;
+    p.count_mapped = r.d_count_mapped;
+    HIPCHK(hipEventRecord(r.ev0, r.stream));
+    for (int fast = 1; fast >= 0; fast--) {
+        p.leaves = r.d_leaves + (fast ? 0 : sh.n_fast);
+        p.n_leaves = fast ? sh.n_fast : (uint32_t)(nl - sh.n_fast);
+        if (!p.n_leaves) continue;
+        p.c.in_range = (uint32_t)fast;
+        p.c.nice_min = fast ? c.nice_min : c.base;
+        const hipError_t err = nice::launch_niceonly_ranges(p, d.num_cus, r.stream);
+        if (err != hipSuccess)
+            return fail(NICE_ERR_HIP, std::string("niceonly ranges launch: ") + hipGetErrorString(err));
+        ++*launches;
+    }
+    HIPCHK(hipEventRecord(r.ev1, r.stream));
+    return NICE_OK;
+}
+
+// Wait for a device's share and add its results: the per-range square
+// survivors and the listed numbers with their range indices.
+int ranges_nice_gather(Device &d, RangesNiceDev &r, const NiceRangesCall &c, const DevShare &sh, uint32_t *launches,
+                       std::vector<uint32_t> &square_ok, std::vector<Entry> &list, double *ms) {
+    HIPCHK(hipSetDevice(d.id));
+    uint32_t cnt = 0;
+    for (int attempt = 0;; attempt++) {
+        HIPCHK(hipStreamSynchronize(r.stream));
+        cnt = *r.h_count;  // published by the last launch's last workgroup
+        if (cnt <= r.list.cap) break;
+        // the device list overflowed: grow it and run the share again
+        if (attempt) return fail(NICE_ERR_HIP, "niceonly ranges list overflow after resize");
+        if (cnt > 0xfffff000u) return fail(NICE_ERR_HIP, "niceonly ranges list longer than 2^32 entries");
+        int rc = ensure_listbuf(d, r.list, (cnt + 4095u) & ~4095u, true);
+        *launches = 0;
+        if (!rc) rc = ranges_nice_enqueue(d, r, c, sh, launches);
+        if (rc) return rc;
+    }
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, r.ev0, r.ev1));
+    *ms = t;
+    std::vector<uint32_t> sq(c.n_ranges);
+    HIPCHK(hipMemcpyAsync(sq.data(), r.d_sq, c.n_ranges * 4, hipMemcpyDeviceToHost, r.stream));
+    std::vector<uint64_t> nbuf((size_t)cnt * 2);
+    std::vector<uint32_t> ubuf(cnt);
+    if (cnt) {
+        HIPCHK(hipMemcpyAsync(nbuf.data(), r.list.n, (size_t)cnt * 16, hipMemcpyDeviceToHost, r.stream));
+        HIPCHK(hipMemcpyAsync(ubuf.data(), r.list.u, (size_t)cnt * 4, hipMemcpyDeviceToHost, r.stream));
+    }
+    HIPCHK(hipStreamSynchronize(r.stream));
+    for (size_t i = 0; i < c.n_ranges; i++) square_ok[i] += sq[i];
+    for (uint32_t q = 0; q < cnt; q++) {
+        if (ubuf[q] >= c.n_ranges) return fail(NICE_ERR_HIP, "self-check: a listed number's range index is out of bounds");
+        list.push_back({mk(nbuf[2 * q], nbuf[2 * q + 1]), ubuf[q]});
+    }
+    return NICE_OK;
+}
+
+int ranges_nice_emit(RangesNiceState &st, uint64_t *candidates, uint32_t *square_ok, nice_number *out,
+                     uint32_t *out_range, size_t cap, size_t *n_out) {
+    if (candidates) std::memcpy(candidates, st.candidates.data(), st.candidates.size() * 8);
+    if (square_ok) std::memcpy(square_ok, st.square_ok.data(), st.square_ok.size() * 4);
+    const size_t n = st.list.size();
+    if (n_out) *n_out = n;
+    if (n > cap) {
+        st.kept = true;
+        return fail(NICE_ERR_CAPACITY,
+                    "output list needs " + std::to_string(n) + " entries, capacity " + std::to_string(cap));
+    }
+    for (size_t i = 0; i < n; i++) {
+        put_entry(out[i], Entry{st.list[i].n, st.base});  // num_uniques = base, like every niceonly entry
+        if (out_range) out_range[i] = st.list[i].u;
+    }
+    st.kept = false;
+    st.bounds = {};
+    st.candidates = {};
+    st.square_ok = {};
+    st.list = {};
+    return NICE_OK;
+}
+
+// Run every device's share: all enqueued, then all gathered.
+int ranges_nice_run(nice_ctx *ctx, RangesNiceState &st, const NiceRangesCall &c, const std::vector<DevShare> &shares) {
+    const size_t nd = ctx->devs.size();
+    std::vector<uint32_t> launches(nd, 0);
+    std::vector<char> queued(nd, 0);
+    auto drain = [&] {
+        for (size_t q = 0; q < nd; q++)
+            if (queued[q]) (void)hipSetDevice(ctx->devs[q].id), (void)hipStreamSynchronize(st.dev[q].stream);
+    };
+    for (size_t dv = 0; dv < nd; dv++) {
+        if (shares[dv].leaves.empty()) continue;
+        int rc = ranges_nice_dev_init(ctx->devs[dv], st.dev[dv]);
+        if (!rc) {
+            queued[dv] = 1;
+            rc = ranges_nice_enqueue(ctx->devs[dv], st.dev[dv], c, shares[dv], &launches[dv]);
+        }
+        if (rc) {
+            drain();
+            return rc;
+        }
+    }
+    for (size_t dv = 0; dv < nd; dv++) {
+        if (!queued[dv]) continue;
+        double ms = 0;
+        const int rc = ranges_nice_gather(ctx->devs[dv], st.dev[dv], c, shares[dv], &launches[dv], st.square_ok,
+                                          st.list, &ms);
+        if (rc) {
+            drain();
+            return rc;
+        }
+        st.stats.launches += launches[dv];
+        st.stats.kernel_ms = std::max(st.stats.kernel_ms, ms);
+    }
+    return NICE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nice_debug_ranges_niceonly_plan(uint32_t base, uint32_t stride_k, const uint64_t *bounds, size_t n_ranges,
+                                    uint32_t n_devices, uint64_t *leaves, size_t cap, size_t *n_out) {
+    if (!bounds || !n_out || (cap && !leaves)) return fail(NICE_ERR_INVALID, "null argument");
+    const uint32_t k = stride_k ? stride_k : 2;
+    if (const char *why = nice::nice_ranges_check(base, n_ranges, k)) return fail(NICE_ERR_INVALID, why);
+    if (n_devices < 1 || n_devices > 64) return fail(NICE_ERR_INVALID, "n_devices must be in 1..64");
+    *n_out = 0;
+    if (nice::residue_filter(base).empty()) return NICE_OK;
+    const std::shared_ptr<nice::StrideTable> table = g_stride.get(base, k);
+    if (table->residues.empty()) return NICE_OK;
+    const nice::NiceRangesPlan pl = nice::plan_nice_ranges(base, k, *table, bounds, n_ranges, n_devices);
+    if (!pl.error.empty()) return fail(NICE_ERR_INVALID, pl.error);
+    *n_out = pl.leaves.size();
+    for (size_t i = 0; i < pl.leaves.size() && i < cap; i++) {
+        const nice::PlanLeaf &l = pl.leaves[i];
+        uint64_t *o = leaves + 7 * i;
+        o[0] = l.b0_lo, o[1] = l.b0_hi, o[2] = l.g0, o[3] = l.count, o[4] = l.range, o[5] = l.group, o[6] = l.device;
+    }
+    return NICE_OK;
+}
+
+int nice_last_ranges_niceonly_stats(nice_ctx *ctx, nice_ranges_niceonly_stats *out) {
+    if (!ctx || !out) return fail(NICE_ERR_INVALID, "bad args");
+    std::lock_guard<std::mutex> lock(ctx->ranges_nice_mu);
+    *out = ctx->ranges_nice.stats;
+    return NICE_OK;
+}
+
+int nice_process_ranges_niceonly(nice_ctx *ctx, uint32_t base, const uint64_t *bounds, size_t n_ranges,
+                                 uint32_t stride_k, uint64_t *candidates, uint32_t *square_ok, nice_number *out,
+                                 uint32_t *out_range, size_t cap, size_t *n_out) {
+    if (!ctx || !bounds || (cap && !out)) return fail(NICE_ERR_INVALID, "null argument");
+    const uint32_t k = stride_k ? stride_k : 2;
+    if (const char *why = nice::nice_ranges_check(base, n_ranges, k)) return fail(NICE_ERR_INVALID, why);
+    for (size_t i = 0; i < n_ranges; i++)
+        if (nice::range_at(bounds, i, 0) >= nice::range_at(bounds, i, 1))
+            return fail(NICE_ERR_INVALID, "range " + std::to_string(i) + " is empty or inverted");
+    std::lock_guard<std::mutex> lock(ctx->ranges_nice_mu);
+    RangesNiceState &st = ctx->ranges_nice;
+    if (st.kept && st.base == base && st.k == k && st.bounds.size() == 4 * n_ranges &&
+        std::equal(st.bounds.begin(), st.bounds.end(), bounds))
+        return ranges_nice_emit(st, candidates, square_ok, out, out_range, cap, n_out);
+    st.kept = false;
+    const size_t nd = ctx->devs.size();
+    st.dev.resize(nd);
+    st.stats = nice_ranges_niceonly_stats{};
+    st.base = base;
+    st.k = k;
+    // as a field submitted now would take it: in range, the compile-time kernels
+    const uint32_t hook = g_nice_min_override[base].load(std::memory_order_relaxed);
+    st.nice_min = hook ? hook : base;
+    st.bounds.assign(bounds, bounds + 4 * n_ranges);
+    st.candidates.assign(n_ranges, 0);
+    st.square_ok.assign(n_ranges, 0);
+    st.list.clear();
+    NiceRangesCall c{base, k, st.nice_min, n_ranges, nullptr};
+    // a residue-empty base (client_process_gpu.rs:525-531), or a table without
+    // a residue: all-zero counts, an empty list, no launch
+    if (!nice::residue_filter(base).empty()) c.table = g_stride.get(base, k);
+    if (c.table && !c.table->residues.empty()) {
+        const nice::NiceRangesPlan pl = nice::plan_nice_ranges(base, k, *c.table, bounds, n_ranges, nd);
+        if (!pl.error.empty()) return fail(NICE_ERR_INVALID, pl.error);
+        st.candidates = pl.candidates;
+        st.stats.fast_ranges = pl.fast_ranges;
+        st.stats.generic_ranges = pl.generic_ranges;
+        st.stats.candidates = pl.total;
+        std::vector<DevShare> shares(nd);
+        for (size_t q = 0; q < pl.leaves.size(); q++) {
+            const nice::PlanLeaf &l = pl.leaves[q];
+            DevShare &sh = shares[l.device];
+            sh.leaves.push_back(nice::RangeLeaf{l.b0_lo, l.b0_hi, l.g0, l.count, l.range, 0});
+            if (q < pl.n_fast_leaves) sh.n_fast++;
+        }
+        if (int rc = ranges_nice_run(ctx, st, c, shares)) return rc;
+        // each range's numbers ascending, in range order (a range's pieces may
+        // have run on several devices)
+        std::sort(st.list.begin(), st.list.end(),
+                  [](const Entry &a, const Entry &b) { return a.u != b.u ? a.u < b.u : a.n < b.n; });
+        for (uint32_t v : st.square_ok) st.stats.square_ok += v;
+    }
+    return ranges_nice_emit(st, candidates, square_ok, out, out_range, cap, n_out);
+}
+
+}  // extern "C"

@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <string>
 #include <thread>
 #include <vector>
@@ -23,6 +24,7 @@
 #include "../../include/nice_hip.h"
 #include "host_math.hpp"
 #include "niceonly_bases.h"
+#include "niceonly_ranges_plan.hpp"
 
 namespace {
 
@@ -109,6 +111,65 @@ void niceonly_range(u128 s, u128 e, const BP &bp, const nice::StrideTable &t,
             cyc++;
         }
     }
+}
+
+// The square's half of is_nice: n^2 has no repeated digit (get_is_nice
+// reaches the cube scan, client_process.rs:222-253).
+template <class BP>
+bool square_free(u128 n, const BP &bp) {
+    uint32_t sq[8], cu[12];
+    nice::MsdFilterT<BP>::powers(n, sq, cu);
+    nice::DigitBuf d;
+    Bits s;
+    nice::digits_of(sq, 8, bp, d);
+    for (int i = 0; i < d.n; i++)
+        if (!s.add(d.d[i])) return false;
+    return true;
+}
+
+// One range of nice_cpu_process_ranges_niceonly: the stride walk of
+// niceonly_range, which also counts the candidates and the repeat-free squares.
+struct RangeAnswer {
+    uint64_t candidates = 0;
+    uint32_t square_ok = 0;
+    std::vector<u128> nice;
+};
+template <class BP>
+void niceonly_range_counted(u128 s, u128 e, const BP &bp, const nice::StrideTable &t, RangeAnswer &out) {
+    const size_t R = t.residues.size();
+    const u128 M = t.modulus;
+    const u128 i0 = t.index_of(s), i1 = t.index_of(e);
+    u128 cyc = i0 / R;
+    size_t r = (size_t)(i0 - cyc * R);
+    out.candidates = (uint64_t)(i1 - i0);
+    for (u128 g = i0; g < i1; g++) {
+        const u128 n = cyc * M + t.residues[r];
+        if (square_free(n, bp)) {
+            out.square_ok++;
+            if (is_nice(n, bp)) out.nice.push_back(n);
+        }
+        if (++r == R) {
+            r = 0;
+            cyc++;
+        }
+    }
+}
+
+int nthreads(int threads, u128 work);
+
+template <class BP>
+void ranges_niceonly_cpu(const BP &bp, const nice::StrideTable &t, const uint64_t *bounds, size_t n_ranges,
+                         int threads, std::vector<RangeAnswer> &ans) {
+    std::atomic<size_t> next{0};
+    auto run = [&] {
+        for (size_t i; (i = next.fetch_add(1)) < n_ranges;)
+            niceonly_range_counted(nice::range_at(bounds, i, 0), nice::range_at(bounds, i, 1), bp, t, ans[i]);
+    };
+    const int nt = nthreads(threads, n_ranges);
+    std::vector<std::thread> ws;
+    for (int i = 0; i + 1 < nt; i++) ws.emplace_back(run);
+    run();  // the caller's thread
+    for (auto &w : ws) w.join();
 }
 
 int nthreads(int threads, u128 work) {
@@ -259,6 +320,52 @@ extern "C" int nice_cpu_process_ranges_detailed(uint32_t base, const uint64_t *b
         out[j] = list[j];
         if (out_range) out_range[j] = idx[j];
     }
+    return NICE_OK;
+}
+
+// nice_process_ranges_niceonly on the host cores: no MSD filter, every stride
+// candidate of every range (stride_filter.rs:139-155) through get_is_nice.
+extern "C" int nice_cpu_process_ranges_niceonly(uint32_t base, const uint64_t *bounds, size_t n_ranges,
+                                                uint32_t stride_k, int32_t threads, uint64_t *candidates,
+                                                uint32_t *square_ok, nice_number *out, uint32_t *out_range,
+                                                size_t cap, size_t *n_out) {
+    if (!bounds || !n_out || (cap && !out)) return cpu_fail(NICE_ERR_INVALID, "null argument");
+    const uint32_t k = stride_k ? stride_k : 2;
+    if (const char *why = nice::nice_ranges_check(base, n_ranges, k)) return cpu_fail(NICE_ERR_INVALID, why);
+    for (size_t i = 0; i < n_ranges; i++)
+        if (nice::range_at(bounds, i, 0) >= nice::range_at(bounds, i, 1))
+            return cpu_fail(NICE_ERR_INVALID, ("range " + std::to_string(i) + " is empty or inverted").c_str());
+    std::vector<RangeAnswer> ans(n_ranges);
+    if (!nice::residue_filter(base).empty()) {  // else: all-zero counts, no list
+        const nice::StrideTable table(base, k);
+        if (!table.residues.empty()) {
+            for (size_t i = 0; i < n_ranges; i++)
+                if (table.index_of(nice::range_at(bounds, i, 1)) - table.index_of(nice::range_at(bounds, i, 0)) >
+                    nice::kNiceRangeCandMax)
+                    return cpu_fail(NICE_ERR_INVALID,
+                                    ("range " + std::to_string(i) + " holds more than 2^40 candidates: use a field")
+                                        .c_str());
+            with_base(base, [&](const auto &bp) {
+                ranges_niceonly_cpu(bp, table, bounds, n_ranges, threads, ans);
+                return 0;
+            });
+        }
+    }
+    size_t total = 0;
+    for (size_t i = 0; i < n_ranges; i++) {
+        if (candidates) candidates[i] = ans[i].candidates;
+        if (square_ok) square_ok[i] = ans[i].square_ok;
+        total += ans[i].nice.size();
+    }
+    *n_out = total;
+    if (total > cap) return cpu_fail(NICE_ERR_CAPACITY, "output capacity too small (n_out = required)");
+    size_t q = 0;
+    for (size_t i = 0; i < n_ranges; i++)
+        for (u128 n : ans[i].nice) {
+            out[q] = nice_number{(uint64_t)n, (uint64_t)(n >> 64), base, 0};
+            if (out_range) out_range[q] = (uint32_t)i;
+            q++;
+        }
     return NICE_OK;
 }
 

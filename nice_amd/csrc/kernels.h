@@ -1,7 +1,8 @@
 // kernels.h -- host-side launch entry points for the gfx950 kernels
 // (implemented in detailed.hip / niceonly.hip / niceonly_part.hip -- the
-// niceonly kernel templates: niceonly_cand.hpp and the headers it lists -- used by
-// the C ABI files, abi_*.cpp).  The word layouts host and device share are in
+// niceonly kernel templates: niceonly_cand.hpp and the headers it lists --,
+// niceonly_ranges.hip / niceonly_ranges_part.hip; used by the C ABI files,
+// abi_*.cpp).  The word layouts host and device share are in
 // layout.h.
 #pragma once
 
@@ -175,6 +176,31 @@ struct SoundLaunch {
 // test runs on the compile-time kernels' in-range fields; elsewhere the
 // variants only leave Filter C out.
 hipError_t launch_niceonly(const NiceonlyLaunch &p, int num_cus, hipStream_t s, const SoundLaunch *snd = nullptr);
+
+// Batched niceonly ranges (niceonly_ranges_kernel, niceonly_ranges.hpp; the
+// run-time-base instance in niceonly_ranges.hip, the fast bases' in the
+// objects of niceonly_ranges_part.hip): niceonly_kernel's walk over leaves
+// that carry the index of the caller's range they belong to.  No MSD filter
+// runs: every stride candidate of every leaf gets the full test.
+struct RangeLeaf {
+    uint64_t b0_lo, b0_hi;  // as Leaf
+    uint32_t g0, count;
+    uint32_t range;         // range index of the call
+    uint32_t pad;
+};
+struct NiceRangesLaunch {
+    NiceonlyLaunch c;          // residues, R, M, base, in_range, nice_min and out, where out.u receives
+                               // each entry's range index; its leaf fields and fin are unused
+    const RangeLeaf *leaves;
+    uint32_t n_leaves;
+    uint32_t *square_ok;       // one counter per range of the call (compile-time kernels only)
+    uint32_t *done;            // kDoneWords arrival counters, re-zeroed by the last workgroup
+    uint32_t *count_mapped;    // ... which copies *c.out.count here (mapped host memory)
+};
+// c.in_range set: the compile-time kernel of c.base (a niceonly fast base, every
+// leaf inside its valid range); else the run-time-base kernel.
+hipError_t launch_niceonly_ranges(const NiceRangesLaunch &p, int num_cus, hipStream_t s);
+
 struct MsdLaunch;
 // Whether a device-MSD field (bounds, base, table and in_range set) can run the
 // prefix test: a niceonly fast base, in range, on the k = 2 table.

@@ -1,0 +1,24 @@
+// niceonly_ranges.hip -- batched niceonly ranges on gfx950: the entry point of
+// kernels.h (launch_niceonly_ranges).  The kernel template is in
+// niceonly_ranges.hpp; this object holds its run-time-base instantiation (any
+// base 2..128, any n < 2^128) and the dispatch to the fast bases' compile-time
+// instantiations, built a few bases per object from niceonly_ranges_part.hip.
+#include "niceonly_bases.h"
+#include "niceonly_ranges.hpp"
+
+namespace nice {
+
+hipError_t launch_niceonly_ranges(const NiceRangesLaunch &rl, int num_cus, hipStream_t s) {
+    if (rl.n_leaves == 0) return hipSuccess;
+    if (rl.c.in_range) {
+        switch (rl.c.base) {
+#define X(b) case b: return RangesBaseLaunch<b>::nice(rl, num_cus, s);
+            NICE_NICEONLY_BASES(X)
+#undef X
+        default: return hipErrorInvalidValue;  // no compile-time kernel: a missing kernel is an error
+        }
+    }
+    return launch_nice_ranges(rl, make_generic(rl.c.base), num_cus, s);
+}
+
+}  // namespace nice

@@ -11,11 +11,21 @@ distributions to: mean and standard deviation of niceness = uniques / base,
 weighted by count (distribution_stats.rs:75-90).
 
     python -m nice_amd --survey --base 50 --windows 4096 --window-size 100000 --gpu
+
+survey_niceonly_base asks the other question of the same windows: what a
+niceonly search of the base would have to do -- how much of it survives the MSD
+filter, how dense the stride candidates are, how many squares survive --
+under the reference filter and under the sound one, through batched niceonly
+calls (GpuContext.niceonly_ranges).
+
+    python -m nice_amd --survey-niceonly --base 50 --windows 4096 --gpu
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import random
+from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
@@ -82,3 +92,102 @@ def survey_base(ctx: Optional[api.GpuContext], base: int, windows: int = 4096,
     near = [(n, u) for n, u, _ in lst]
     mean, stdev = mean_stdev(dist, base)
     return SurveyResult(base, w, dist, near, mean, stdev)
+
+
+# ranges per batched niceonly call (the library takes at most 2^20)
+NICEONLY_BATCH = 1 << 20
+
+
+@dataclass
+class NiceonlyFilterSurvey:
+    """What one MSD filter leaves of the sampled windows."""
+    filter: str          # "reference" or "sound"
+    msd_ranges: int      # MSD-surviving ranges
+    msd_numbers: int     # numbers inside them
+    candidates: int      # their stride candidates (k = 2)
+    square_ok: int       # ... with a repeat-free square
+    found: List[int]     # the numbers that passed, window by window
+
+    def counts(self) -> dict:
+        return {"msd_ranges": self.msd_ranges, "msd_numbers": self.msd_numbers, "candidates": self.candidates,
+                "square_ok": self.square_ok, "found": len(self.found)}
+
+
+@dataclass
+class NiceonlySurveyResult:
+    base: int
+    windows: List[Tuple[int, int]]   # the sampled [start, end)
+    msd_floor: int
+    range_size: int                  # numbers in the base's valid range
+    sampled: int                     # numbers in the windows
+    reference: NiceonlyFilterSurvey
+    sound: NiceonlyFilterSurvey
+
+    def scaled(self, which: str) -> dict:
+        """A filter's counts (and the sampled numbers) scaled to the whole base
+        range: count * range_size / sampled."""
+        out = {k: v * self.range_size / self.sampled for k, v in getattr(self, which).counts().items()}
+        out["sampled"] = float(self.range_size)
+        return out
+
+
+def _msd_ranges(window, base, floor, filt):
+    s, e = window
+    if e - s <= floor:  # get_valid_ranges_recursive emits such a range untested
+        return [window]
+    return [(r.range_start, r.range_end)
+            for r in api.get_valid_ranges(api.FieldSize(s, e), base, floor, filt)]
+
+
+def survey_niceonly_base(ctx: Optional[api.GpuContext], base: int, windows: int = 4096,
+                         window_size: int = 10 ** 6, seed: int = 0, msd_floor: int = 250,
+                         threads: int = 1) -> NiceonlySurveyResult:
+    """What a niceonly search of `base` would cost, from the stratified windows
+    of survey_windows.  Per window the MSD filter (nice_msd_valid_ranges_ex,
+    floor msd_floor) runs on `threads` host threads, once under the reference
+    filter and once under the sound one; the surviving ranges of all windows
+    go through batched niceonly calls (ctx.niceonly_ranges; ctx=None: the CPU
+    twin on `threads` threads).  Reported per filter: MSD-surviving ranges and
+    numbers, stride candidates, square survivors and the numbers found, and
+    through scaled() each of these scaled to the whole base range.  No time
+    estimate: nothing here has measured one.
+
+    The sound column counts the candidates of the ranges the sound MSD filter
+    leaves, i.e. BEFORE the field path's per-candidate prefix test, which
+    rejects some of them ahead of the square test (that test needs the MSD
+    leaf's mask and does not run on ranges handed in from outside).
+    square_ok is counted on the GPU only for a niceonly fast base (k = 2,
+    ranges inside the valid range -- every window is); elsewhere it reads 0
+    there, while the CPU twin counts it for every base.
+    Deterministic in `seed`."""
+    w = survey_windows(base, windows, window_size, seed)
+    r = api.get_base_range_u128(base)
+    # windows no larger than the floor: the MSD recursion emits each untested
+    # (see _msd_ranges), under either filter
+    small = all(e - s <= msd_floor for s, e in w)
+    per_filter = {}
+    with ThreadPoolExecutor(max(1, threads)) as pool:
+        for filt in ("reference", "sound"):
+            if small and per_filter:
+                per_filter[filt] = dataclasses.replace(per_filter["reference"], filter=filt)
+                continue
+            if small:
+                ranges = list(w)
+            else:
+                ranges = [x for rs in pool.map(lambda win: _msd_ranges(win, base, msd_floor, filt), w)
+                          for x in rs]
+            cand = sq = 0
+            found: List[int] = []
+            for i in range(0, len(ranges), NICEONLY_BATCH):
+                part = ranges[i:i + NICEONLY_BATCH]
+                if ctx is None:
+                    c, q, lst = api.niceonly_ranges_cpu(part, base, threads=threads)
+                else:
+                    c, q, lst = ctx.niceonly_ranges(part, base)
+                cand += sum(c)
+                sq += sum(q)
+                found += [n for n, _ in lst]
+            per_filter[filt] = NiceonlyFilterSurvey(filt, len(ranges), sum(b - a for a, b in ranges), cand, sq,
+                                                    found)
+    return NiceonlySurveyResult(base, w, msd_floor, r.range_end - r.range_start, sum(b - a for a, b in w),
+                                per_filter["reference"], per_filter["sound"])

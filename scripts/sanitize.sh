@@ -22,6 +22,15 @@ for san in asan tsan; do
     TSAN_OPTIONS=halt_on_error=1:second_deadlock_stack=1 \
         python3 -m pytest $TESTS -q -m "not gpu" -p no:cacheprovider "$@"
 done
+# The batched niceonly ranges' host code (the leaf plan, niceonly_ranges_plan.hpp,
+# and the CPU twin in cpu_path.cpp) as a program with its own main: ASan + UBSan
+# linked in, run as it is (no Python, nothing preloaded).
+echo "=== asan+ubsan: tests/ranges_niceonly_san.cpp"
+mkdir -p nice_amd/build/asan
+${CXX:-c++} -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
+    -I nice_amd/csrc tests/ranges_niceonly_san.cpp nice_amd/csrc/cpu_path.cpp -o nice_amd/build/asan/ranges_niceonly_san -lpthread
+ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
+    nice_amd/build/asan/ranges_niceonly_san
 # Canary: the ASan build must report a deliberate heap overflow (a 32-byte
 # histogram buffer where base 40 needs 41 u64 bins), or the runs above prove
 # nothing.
