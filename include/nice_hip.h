@@ -516,6 +516,66 @@ int nice_debug_ranges_niceonly_plan(uint32_t base, uint32_t stride_k, const uint
                                     size_t n_ranges, uint32_t n_devices, uint64_t *leaves,
                                     size_t cap, size_t *n_out);
 
+/* The per-number map: out[i] = the unique-digit count of n^2 and n^3 of
+ * n = start + i, the value get_num_unique_digits returns
+ * (client_process.rs:47-143) -- 1..base, one byte for every base <= 128 --
+ * for every n of [start, end), at most 2^32 of them.  Every aggregate the
+ * other calls return follows from it: bincount(out) is
+ * nice_process_range_detailed's histogram of the range, the positions with
+ * out[i] > nice_near_miss_cutoff(base) its list; and so does every statistic
+ * they do not return (the count against n mod (b - 1), against the low or the
+ * leading digits) without further device code.
+ * Any base 2..128 and any n: the parts of the range inside the valid range of
+ * a base with an FD kernel (nice_fd_kernel_base) run that kernel's arithmetic
+ * (fd2_map_kernel: the limb walk of the detailed kernel, a byte stored per n
+ * instead of the histogram), cut at the limb layouts nice_fd_segment_cuts
+ * reports; every other part runs the generic per-n device function.
+ * nice_map_stats says which ran.
+ *   NICE_MAP_HOST: `out` is host memory.  The range is sharded contiguously
+ *     over the context's devices, as fields are, and each shard copied back.
+ *     device_index is ignored.
+ *   NICE_MAP_DEVICE: `out` is device memory on the context's device number
+ *     device_index (an index into the list the context was created with), of
+ *     any byte alignment.  That device writes the map in place; the call
+ *     returns after its stream is idle, so any stream of the caller may read
+ *     `out` straight away.  No byte outside out[0, end - start) is written.
+ * Errors: NICE_ERR_INVALID (an empty or inverted range, base outside 2..128,
+ * more than 2^32 numbers, a flag other than the two, a device_index outside
+ * the context in device mode, a null out), NICE_ERR_CAPACITY (cap < end -
+ * start: nothing is written).
+ * The call has its own stream, buffers and lock per device: it takes no
+ * detailed or niceonly slot and does not wait for fields in flight.  There is
+ * no list, so nice_debug_set_near_miss_cutoff and the other hooks do not
+ * apply. */
+#define NICE_MAP_HOST 0
+#define NICE_MAP_DEVICE 1
+int nice_unique_map(nice_ctx *ctx, uint64_t start_lo, uint64_t start_hi, uint64_t end_lo,
+                    uint64_t end_hi, uint32_t base, uint8_t *out, size_t cap, uint32_t flags,
+                    int device_index);
+/* The same on the host cores (no device): get_num_unique_digits per n, the
+ * range split contiguously over `threads`.  The same errors. */
+int nice_cpu_unique_map(uint64_t start_lo, uint64_t start_hi, uint64_t end_lo, uint64_t end_hi,
+                        uint32_t base, int32_t threads, uint8_t *out, size_t cap);
+typedef struct {
+    uint32_t launches;         /* kernel launches of the last call */
+    uint32_t fd_segments;      /* pieces run by the FD map kernel (one per limb layout and device) */
+    uint32_t generic_segments; /* pieces run by the generic per-n kernel */
+    uint32_t reserved;
+    uint64_t fd_numbers;
+    uint64_t generic_numbers;
+    double kernel_ms;          /* HIP events around the launches (the slowest device) */
+} nice_map_stats;
+int nice_last_map_stats(nice_ctx *ctx, nice_map_stats *out);
+/* Test hook (no device): the plan of nice_unique_map for [start, end) on one
+ * device.  Writes 8 u64 per record, in ascending n: kind (0: a workgroup of
+ * the FD map kernel, 1: a generic segment), start_lo, start_hi, the output
+ * offset of the record's first number (n - start), lanes, chunk (numbers per
+ * lane; a generic segment: 0, 0), combo index (the limb layout: the index of
+ * the nice_fd_segment_cuts interval), numbers covered (FD: lanes * chunk).
+ * *n_out = the true count.  The same argument errors as nice_unique_map. */
+int nice_debug_map_plan(uint32_t base, uint64_t start_lo, uint64_t start_hi, uint64_t end_lo,
+                        uint64_t end_hi, uint64_t *records, size_t cap, size_t *n_out);
+
 /* Diagnostics: per-n results of the device functions the kernels use. */
 int nice_debug_unique_counts(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t count,
                              uint32_t base, uint32_t *out);

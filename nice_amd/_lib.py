@@ -31,6 +31,9 @@ NICE_FILTER_SOUND = 1
 # nice_process_ranges_detailed flags: one histogram row per range, or their sum
 NICE_RANGES_PER_RANGE = 0
 NICE_RANGES_SUM = 1
+# nice_unique_map flags: `out` is host memory, or device memory of one of the context's devices
+NICE_MAP_HOST = 0
+NICE_MAP_DEVICE = 1
 
 # Every symbol include/nice_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -53,6 +56,7 @@ EXPORTS = (
     "nice_debug_set_nice_min", "nice_debug_cube_count", "nice_debug_force_sib_persistent",
     "nice_process_ranges_niceonly", "nice_last_ranges_niceonly_stats", "nice_cpu_process_ranges_niceonly",
     "nice_debug_ranges_niceonly_plan",
+    "nice_unique_map", "nice_cpu_unique_map", "nice_last_map_stats", "nice_debug_map_plan",
 )
 
 
@@ -102,6 +106,13 @@ class nice_ranges_niceonly_stats(ctypes.Structure):
     _fields_ = [("launches", ctypes.c_uint32), ("fast_ranges", ctypes.c_uint32),
                 ("generic_ranges", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("candidates", ctypes.c_uint64), ("square_ok", ctypes.c_uint64),
+                ("kernel_ms", ctypes.c_double)]
+
+
+class nice_map_stats(ctypes.Structure):
+    _fields_ = [("launches", ctypes.c_uint32), ("fd_segments", ctypes.c_uint32),
+                ("generic_segments", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("fd_numbers", ctypes.c_uint64), ("generic_numbers", ctypes.c_uint64),
                 ("kernel_ms", ctypes.c_double)]
 
 
@@ -191,6 +202,11 @@ def lib():
         "nice_last_ranges_niceonly_stats": ([vp, ctypes.POINTER(nice_ranges_niceonly_stats)], i32),
         "nice_cpu_process_ranges_niceonly": ([u32, P64, sz, u32, i32, P64, P32, PN, P32, sz, PSZ], i32),
         "nice_debug_ranges_niceonly_plan": ([u32, u32, P64, sz, u32, P64, sz, PSZ], i32),
+        # `out` as an address: a numpy buffer's or a torch tensor's data_ptr()
+        "nice_unique_map": ([vp, u64, u64, u64, u64, u32, vp, sz, u32, i32], i32),
+        "nice_cpu_unique_map": ([u64, u64, u64, u64, u32, i32, vp, sz], i32),
+        "nice_last_map_stats": ([vp, ctypes.POINTER(nice_map_stats)], i32),
+        "nice_debug_map_plan": ([u32, u64, u64, u64, u64, P64, sz, PSZ], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

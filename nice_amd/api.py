@@ -185,6 +185,16 @@ class RangesStats:
 
 
 @dataclass
+class MapStats:
+    launches: int          # kernel launches of the call
+    fd_segments: int       # pieces run by the FD map kernel (one per limb layout and device)
+    generic_segments: int  # pieces run by the generic per-n kernel
+    fd_numbers: int
+    generic_numbers: int
+    kernel_ms: float       # HIP events around the launches (the slowest device)
+
+
+@dataclass
 class RangesNiceonlyStats:
     launches: int        # kernel launches of the call (at most two per device)
     fast_ranges: int     # ranges run by the base's compile-time kernel (square_ok counted)
@@ -347,6 +357,50 @@ class GpuContext:
         s = _lib.nice_ranges_stats()
         check(lib().nice_last_ranges_stats(self._h, s))
         return RangesStats(s.launches, s.fallback_ranges, s.numbers, s.kernel_ms)
+
+    # -- the per-number map ------------------------------------------------------
+    def unique_map(self, start: int, end: int, base: int, out=None):
+        """The unique-digit count of n^2 and n^3 of every n in [start, end), one
+        byte per number (nice_unique_map; at most 2^32 numbers).  With out=None
+        the range is sharded over the context's GPUs and returned as a
+        numpy.uint8 array.  With `out` a contiguous torch.uint8 tensor on one
+        of the context's GPUs, at least end - start long (any storage offset),
+        the map is written in place through its data_ptr() and `out` is
+        returned.  The call returns only after the library's own stream has
+        finished writing, so the caller's current torch stream -- any stream --
+        may use the tensor straight away; work already queued on `out` by the
+        caller must have finished before the call.  (torch and the library
+        share one HIP runtime only when torch was imported, and found the GPU,
+        before the library was first loaded -- bench.py's order; the other way
+        round torch sees no device and there is no such tensor to pass.)
+        bincount of the map is the detailed histogram of the range; see
+        map_stats() for what ran."""
+        size = end - start
+        if out is None:
+            import numpy as np
+            buf = np.empty(max(size, 0), dtype=np.uint8)
+            check(lib().nice_unique_map(self._h, *_split(start), *_split(end), base, buf.ctypes.data or None,
+                                        buf.size, _lib.NICE_MAP_HOST, 0))
+            return buf
+        import torch
+        if not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.is_cuda and out.dim() == 1
+                and out.is_contiguous()):
+            raise ValueError("out must be a contiguous one-dimensional torch.uint8 tensor on a GPU")
+        if out.device.index not in self.devices:
+            raise ValueError(f"out lives on {out.device}, which is not one of the context's devices")
+        # (the producer of `out`'s current contents, if any, is the caller's:
+        # the library's stream does not wait for torch's)
+        torch.cuda.current_stream(out.device).synchronize()
+        check(lib().nice_unique_map(self._h, *_split(start), *_split(end), base, out.data_ptr() or None,
+                                    out.numel(), _lib.NICE_MAP_DEVICE, self.devices.index(out.device.index)))
+        return out
+
+    def map_stats(self) -> "MapStats":
+        """Statistics of this context's last unique_map call."""
+        s = _lib.nice_map_stats()
+        check(lib().nice_last_map_stats(self._h, s))
+        return MapStats(s.launches, s.fd_segments, s.generic_segments, s.fd_numbers, s.generic_numbers,
+                        s.kernel_ms)
 
     # -- batched niceonly ranges ------------------------------------------------
     def niceonly_ranges(self, ranges, base: int, stride_k: int = 0, cap: int = 0):
@@ -631,6 +685,15 @@ def process_range_detailed_cpu(range_: FieldSize, base: int, threads: int = 1) -
         distribution=[UniquesDistributionSimple(i, hist[i]) for i in range(1, base + 1)],
         nice_numbers=[NiceNumberSimple(out[i].number_lo | (out[i].number_hi << 64), out[i].num_uniques)
                       for i in range(n.value)])
+
+
+def unique_map_cpu(start: int, end: int, base: int, threads: int = 1):
+    """GpuContext.unique_map on the host cores (nice_cpu_unique_map): no
+    device.  Returns a numpy.uint8 array."""
+    import numpy as np
+    buf = np.empty(max(end - start, 0), dtype=np.uint8)
+    check(lib().nice_cpu_unique_map(*_split(start), *_split(end), base, threads, buf.ctypes.data or None, buf.size))
+    return buf
 
 
 def detailed_ranges_cpu(ranges, base: int, sum: bool = False, threads: int = 1):

@@ -21,6 +21,8 @@ merged in chunk order (compile_results).  No GPU is touched in that mode.
     python -m nice_amd --benchmark base-ten            # CPU mode
     python -m nice_amd --survey --base 50 --gpu        # distribution of a sampled base range
     python -m nice_amd --survey-niceonly --base 50 --gpu   # what a niceonly search of the base would cost
+    python -m nice_amd --survey-classes 49 --base 50 --gpu # the distribution split by n mod 49
+    python -m nice_amd --map out.npy --base 40 --range S E --gpu   # the unique count of every n of a range
 """
 from __future__ import annotations
 
@@ -82,6 +84,13 @@ def parse_args(argv=None):
                         "and numbers found in the same stratified windows, under the reference and the sound "
                         "filter (nice_amd/survey.py survey_niceonly_base); with --gpu on the GPU; --msd-floor "
                         "as a number (0 = 250)")
+    p.add_argument("--survey-classes", type=int, default=None, metavar="M",
+                   help="survey --base by residue class: the table [n mod M][num_uniques] of the same "
+                        "stratified windows, from the per-number map (nice_amd/survey.py class_distribution); "
+                        "with --gpu computed on the GPU")
+    p.add_argument("--map", default=None, metavar="OUT.npy",
+                   help="write the per-number map of --range/--base (one uint8 per n: its unique-digit count) "
+                        "as a .npy file; with --gpu on the GPU, else on --threads host threads")
     p.add_argument("--windows", type=int, default=4096, help="--survey, --survey-niceonly: sample windows (strata)")
     p.add_argument("--window-size", type=int, default=None,
                    help="numbers per window (--survey: 100000, --survey-niceonly: 1000000)")
@@ -242,6 +251,40 @@ def run_survey_niceonly(args, ctx) -> int:
     return 0
 
 
+def run_survey_classes(args, ctx) -> int:
+    """--survey-classes M: print the table [n mod M][num_uniques] of --base as one JSON line."""
+    from .survey import class_distribution
+    if not args.base or args.survey_classes < 1:
+        log.error("--survey-classes needs --base and a positive modulus")
+        return 2
+    t0 = time.perf_counter()
+    table = class_distribution(ctx, args.base, args.survey_classes, args.windows, args.window_size, args.seed,
+                               threads=max(1, args.threads))
+    elapsed = time.perf_counter() - t0
+    numbers = sum(sum(row) for row in table)
+    log.info("✓ Surveyed %.2e numbers of base %d by n mod %d in %.2fs", numbers, args.base, args.survey_classes,
+             elapsed)
+    print(json.dumps({"base": args.base, "modulus": args.survey_classes, "windows": args.windows,
+                      "window_size": args.window_size, "seed": args.seed, "numbers": numbers, "table": table}))
+    return 0
+
+
+def run_map(args, ctx) -> int:
+    """--map OUT.npy: the per-number map of --range/--base."""
+    import numpy as np
+    if not (args.range and args.base):
+        log.error("--map needs --base and --range")
+        return 2
+    s, e = args.range
+    t0 = time.perf_counter()
+    m = ctx.unique_map(s, e, args.base) if ctx is not None else api.unique_map_cpu(s, e, args.base,
+                                                                                   max(1, args.threads))
+    elapsed = time.perf_counter() - t0
+    np.save(args.map, m)
+    log.info("✓ Mapped %.2e numbers of base %d in %.2fs -> %s", e - s, args.base, elapsed, args.map)
+    return 0
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     level = {"off": logging.CRITICAL + 10, "error": logging.ERROR, "warn": logging.WARNING,
@@ -250,6 +293,11 @@ def main(argv=None) -> int:
     ctx = None
     if args.gpu:  # main.rs:592-625: the GPU context only in GPU mode
         log.info("GPU_BATCH_SIZE = %d", api.GPU_BATCH_SIZE)
+        if args.survey_classes is not None:
+            # the class survey bins the map with torch on the device: torch has to load its HIP
+            # runtime before the library loads, so that the two share one (survey.class_distribution)
+            import torch
+            torch.cuda.init()
         try:
             ctx = api.GpuContext(_devices(args.gpu_device))
         except api._lib.NiceError as e:
@@ -261,6 +309,10 @@ def main(argv=None) -> int:
         return run_survey(args, ctx)
     if args.survey_niceonly:
         return run_survey_niceonly(args, ctx)
+    if args.survey_classes is not None:
+        return run_survey_classes(args, ctx)
+    if args.map:
+        return run_map(args, ctx)
     while True:
         rc = run_once(args, ctx)
         if rc or not args.repeat:

@@ -21,6 +21,7 @@
 //   abi_niceonly.cpp   niceonly fields: device MSD or host MSD producer
 //   abi_ranges.cpp     batched detailed ranges
 //   abi_ranges_niceonly.cpp  batched niceonly ranges
+//   abi_map.cpp        the per-number unique-count map
 //   abi_hooks.cpp      debug and check hooks
 //   host_parallel.cpp  host thread count and the adaptive MSD floor (no HIP)
 #pragma once
@@ -251,10 +252,27 @@ struct RangesNiceState {
     std::vector<Entry> list;  // Entry::u: the range index
 };
 
+// nice_unique_map: likewise one stream and its buffers per device, apart from
+// the slots.
+struct MapDev {
+    hipStream_t stream = nullptr;
+    void *h_desc = nullptr, *d_desc = nullptr;  // pinned / device descriptors
+    size_t desc_cap = 0;                        // FD records
+    uint8_t *d_out = nullptr;                   // host mode: the device's shard of the map
+    size_t out_cap = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+struct MapState {
+    std::vector<MapDev> dev;
+    nice_map_stats stats{};
+};
+
 }  // namespace abi
 }  // namespace nice
 
 struct nice_ctx {
+    std::mutex map_mu;  // serialises nice_unique_map (not ctx->mu: fields in flight go on)
+    nice::abi::MapState map;
     std::mutex ranges_mu;  // serialises nice_process_ranges_detailed (not ctx->mu: fields in flight go on)
     nice::abi::RangesState ranges;
     std::mutex ranges_nice_mu;  // ... and nice_process_ranges_niceonly
@@ -501,6 +519,8 @@ int resolve_stats(Device &d);
 void ranges_dev_free(Device &d, RangesDev &r);
 // abi_ranges_niceonly.cpp: likewise.
 void ranges_nice_dev_free(Device &d, RangesNiceDev &r);
+// abi_map.cpp: likewise.
+void map_dev_free(Device &d, MapDev &r);
 
 }  // namespace abi
 }  // namespace nice

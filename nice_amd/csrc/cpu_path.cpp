@@ -277,6 +277,32 @@ extern "C" int nice_cpu_process_range_detailed(uint64_t start_lo, uint64_t start
     return with_base(base, [&](const auto &bp) { return detailed_cpu(s, e, bp, threads, hist, out, cap, n_out); });
 }
 
+// nice_unique_map on the host cores: get_num_unique_digits per n
+// (client_process.rs:47-143), the range split contiguously over the threads.
+extern "C" int nice_cpu_unique_map(uint64_t start_lo, uint64_t start_hi, uint64_t end_lo, uint64_t end_hi,
+                                   uint32_t base, int32_t threads, uint8_t *out, size_t cap) {
+    if (!out) return cpu_fail(NICE_ERR_INVALID, "null out");
+    if (base < 2 || base > 128) return cpu_fail(NICE_ERR_INVALID, "base must be in 2..=128");
+    const u128 s = mk(start_lo, start_hi), e = mk(end_lo, end_hi);
+    if (s >= e) return cpu_fail(NICE_ERR_INVALID, "range is empty or inverted");
+    const u128 size = e - s;
+    if (size > ((u128)1 << 32)) return cpu_fail(NICE_ERR_INVALID, "more than 2^32 numbers: map the range in pieces");
+    if ((u128)cap < size) return cpu_fail(NICE_ERR_CAPACITY, "the map needs end - start bytes");
+    return with_base(base, [&](const auto &bp) {
+        const int nt = nthreads(threads, size);
+        auto piece = [&](int i) {
+            const u128 a = size / nt * i + std::min<u128>(i, size % nt);
+            const u128 b = size / nt * (i + 1) + std::min<u128>(i + 1, size % nt);
+            for (u128 k = a; k < b; k++) out[(size_t)k] = (uint8_t)unique_digits(s + k, bp);
+        };
+        std::vector<std::thread> ws;
+        for (int i = 0; i + 1 < nt; i++) ws.emplace_back(piece, i);
+        piece(nt - 1);  // the caller's thread
+        for (auto &w : ws) w.join();
+        return (int)NICE_OK;
+    });
+}
+
 // The batched-ranges call on the host cores: the CPU path range by range.
 extern "C" int nice_cpu_process_ranges_detailed(uint32_t base, const uint64_t *bounds, size_t n_ranges,
                                                 uint32_t flags, int32_t threads, uint64_t *hist,

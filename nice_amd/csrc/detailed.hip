@@ -12,8 +12,10 @@
 //   Per-n multiply + chunked radix extraction with a runtime base.  Used for
 //   segments outside the valid range (e.g. the reference's b10 @ 1e6 GPU
 //   test, client_process_gpu.rs:1485) and for bases without an FD instance.
+// generic_map_kernel  (the same per-n function, one byte per n: nice_unique_map)
 #include "kernels.h"
 #include "nice_device.hpp"
+#include "unique_map.h"
 
 namespace nice {
 
@@ -55,6 +57,19 @@ detailed_generic_kernel(u64 start_lo, u64 start_hi, u64 count, GenericBase g, u3
 __global__ void unique_counts_kernel(const u64 *n_pairs, u32 count, GenericBase g, u32 *out) {
     u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) out[i] = unique_generic(n_pairs[2 * i], n_pairs[2 * i + 1], g);
+}
+
+// The per-number map outside the FD kernel's reach (a base without an FD
+// instance, n outside the base's valid range): out[i] = the unique-digit count
+// of start + i, one thread per n.  Consecutive threads write consecutive
+// bytes: a wave's store covers 64 contiguous bytes whatever `out`'s alignment.
+__global__ void __launch_bounds__(256)
+generic_map_kernel(u64 start_lo, u64 start_hi, u64 count, GenericBase g, unsigned char *__restrict__ out) {
+    const u64 idx = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= count) return;
+    u64 lo = start_lo, hi = start_hi;
+    add_u128(lo, hi, idx);
+    out[idx] = (unsigned char)unique_generic(lo, hi, g);
 }
 
 // Field epilogue: sum the kHistCopies histogram copies into `out` (kHistBins
@@ -99,6 +114,15 @@ hipError_t launch_detailed_generic(const DetailedLaunch &p, int num_cus, hipStre
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(detailed_generic_kernel, dim3((u32)grid), dim3(256), 0, s, p.start_lo,
                        p.start_hi, p.count, g, p.cutoff, p.hist, p.out);
+    return hipGetLastError();
+}
+
+hipError_t launch_generic_map(uint64_t start_lo, uint64_t start_hi, uint64_t count, uint32_t base, uint8_t *out,
+                              hipStream_t s) {
+    if (!count || count > ((u64)1 << 32)) return hipErrorInvalidValue;
+    GenericBase g = make_generic(base);
+    hipLaunchKernelGGL(generic_map_kernel, dim3((u32)((count + 255) / 256)), dim3(256), 0, s, start_lo, start_hi,
+                       count, g, out);
     return hipGetLastError();
 }
 

@@ -8,6 +8,8 @@
 
 #include "fd2_combos.h"
 #include "fd2_launch.hpp"
+#include "fd2_map_kernel.hpp"
+#include "unique_map.h"
 
 namespace nice {
 namespace fd2 {
@@ -275,6 +277,87 @@ hipError_t launch_detailed_fd2_batch(const BatchLaunch &p, hipStream_t s) {
         err = parts[fd2_part_of((int)p.base)](p, cb.nd, cb.ne, cb.ne2,
                                               (const fd2::Fd2Unit *)p.d_desc + first[c], (uint32_t)n, s);
         if (err != hipSuccess) return err == hipErrorNotFound ? hipErrorInvalidValue : err;
+    }
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------
+// Unique-count map (fd2_map_kernel.hpp; the launchers in fd2_map_part.hip).
+// ---------------------------------------------------------------------------
+namespace fd2 {
+using MapFn = hipError_t (*)(uint32_t, int, int, int, const void *, uint32_t, unsigned char *, hipStream_t);
+hipError_t launch_map_part0(uint32_t, int, int, int, const void *, uint32_t, unsigned char *, hipStream_t);
+hipError_t launch_map_part1(uint32_t, int, int, int, const void *, uint32_t, unsigned char *, hipStream_t);
+hipError_t launch_map_part2(uint32_t, int, int, int, const void *, uint32_t, unsigned char *, hipStream_t);
+hipError_t launch_map_part3(uint32_t, int, int, int, const void *, uint32_t, unsigned char *, hipStream_t);
+hipError_t launch_map_part4(uint32_t, int, int, int, const void *, uint32_t, unsigned char *, hipStream_t);
+hipError_t launch_map_part5(uint32_t, int, int, int, const void *, uint32_t, unsigned char *, hipStream_t);
+static_assert(FD2_NPARTS == 6, "launch_map_part declarations");
+}  // namespace fd2
+
+// The map kernel is the batch kernel's configuration (MapCfg): its workgroup
+// size and its odd target chunk.
+MapBase map_base(uint32_t base) {
+    MapBase b;
+    u128 rs = 0, re = 0;
+    if (!fd2_supported(base) || base_range_cached(base, rs, re) != 1) return b;
+    b.fd = true;
+    b.rs = rs;
+    b.re = re;
+    b.cuts = fd2::thresholds(base).cuts;
+    b.wg = fd2_batch_wg(base);
+    b.tchunk = fd2_batch_chunk(base);
+    return b;
+}
+
+hipError_t launch_unique_map(const MapLaunch &p, hipStream_t s) {
+    const bool fd = fd2_supported(p.base);
+    const fd2::BaseThresholds *t = fd ? &fd2::thresholds(p.base) : nullptr;
+    const u32 B = p.base * p.base;
+    const int dn = fd2::digits_of((int)p.base).dn, nx = cdiv(dn, 2);  // Cfg::DN, NX
+    // init_at reads the digits only where n passes 64 bits and the kernel
+    // keeps 32-bit init columns (Cfg::N64, C64)
+    const bool digits = fd && !fd2::fits64(p.base, dn) && fd2_batch_wg(p.base) < 1024;
+    fd2::Fd2MapUnit *h = (fd2::Fd2MapUnit *)p.h_desc;
+    static_assert(sizeof(fd2::Fd2MapUnit) == kMapDescBytes, "descriptor size");
+    size_t nu = 0;
+    for (size_t i = 0; i < p.n_recs; i++) {
+        const MapRec &r = p.recs[i];
+        if (r.kind != kMapFd) continue;
+        if (!fd || r.combo >= t->combos.size()) return hipErrorInvalidValue;
+        fd2::Fd2MapUnit &d = h[nu++];
+        d.lo = r.lo;
+        d.hi = r.hi;
+        d.off = r.off;
+        d.lanes = r.lanes;
+        d.chunk = r.chunk;
+        for (int k = 0; k < fd2::kXDigits; k++) d.xs[k] = 0;
+        if (digits) fd2::host_digits(((u128)r.hi << 64) | r.lo, B, d.xs, nx);
+    }
+    hipError_t err;
+    if (nu && (err = hipMemcpyAsync(p.d_desc, p.h_desc, nu * kMapDescBytes, hipMemcpyHostToDevice, s)) != hipSuccess)
+        return err;
+    static const fd2::MapFn parts[FD2_NPARTS] = {fd2::launch_map_part0, fd2::launch_map_part1,
+                                                 fd2::launch_map_part2, fd2::launch_map_part3,
+                                                 fd2::launch_map_part4, fd2::launch_map_part5};
+    size_t at = 0;  // FD records before record i
+    for (size_t i = 0; i < p.n_recs;) {
+        const MapRec &r = p.recs[i];
+        if (r.kind != kMapFd) {
+            if ((err = launch_generic_map(r.lo, r.hi, r.count, p.base, p.out + r.off, s)) != hipSuccess) return err;
+            i++;
+        } else {
+            size_t j = i;  // the run of FD records of this limb layout
+            while (j < p.n_recs && p.recs[j].kind == kMapFd && p.recs[j].combo == r.combo) j++;
+            if (j - i > 0x7fffffffull) return hipErrorInvalidValue;
+            const fd2::Combo &cb = t->combos[r.combo];
+            err = parts[fd2_part_of((int)p.base)](p.base, cb.nd, cb.ne, cb.ne2,
+                                                  (const fd2::Fd2MapUnit *)p.d_desc + at, (uint32_t)(j - i), p.out, s);
+            if (err != hipSuccess) return err == hipErrorNotFound ? hipErrorInvalidValue : err;
+            at += j - i;
+            i = j;
+        }
+        if (p.launches) ++*p.launches;
     }
     return hipSuccess;
 }

@@ -94,6 +94,49 @@ def survey_base(ctx: Optional[api.GpuContext], base: int, windows: int = 4096,
     return SurveyResult(base, w, dist, near, mean, stdev)
 
 
+def class_distribution(ctx: Optional[api.GpuContext], base: int, modulus: int, windows: int = 4096,
+                       window_size: int = 100_000, seed: int = 0, threads: int = 1) -> List[List[int]]:
+    """The unique-digit distribution of survey_windows' sample split by residue
+    class: table[c][u] = the sampled numbers n with n % modulus == c and u unique
+    digits (rows 0..modulus-1, bins 0..base).  Summed over the classes it is
+    survey_base's distribution for the same windows and seed.  This is the
+    conditioning behind the reference's residue filter (modulus = base - 1) and
+    its low-digit filters (modulus = base, base^2).
+
+    On a GPU context everything stays on the device: each window's map
+    (GpuContext.unique_map into a torch tensor) is binned with torch.bincount
+    of cls * (base + 1) + u; no device code beyond the map.  For that, torch
+    and the library must share one HIP runtime: import torch (and let it find
+    the GPU) BEFORE the library is first loaded, as bench.py does -- a library
+    loaded first brings the system's runtime, torch then loads its own copy
+    and finds no device.  ctx=None: the CPU twin's maps (`threads` host
+    threads), binned with numpy.  Deterministic in `seed`."""
+    if modulus < 1:
+        raise ValueError("modulus must be positive")
+    w = survey_windows(base, windows, window_size, seed)
+    nb = base + 1
+    if ctx is None:
+        import numpy as np
+        table = np.zeros(modulus * nb, dtype=np.int64)
+        for s, e in w:
+            u = api.unique_map_cpu(s, e, base, threads).astype(np.int64)
+            cls = (np.arange(e - s, dtype=np.int64) + s % modulus) % modulus
+            table += np.bincount(cls * nb + u, minlength=modulus * nb)
+        return table.reshape(modulus, nb).tolist()
+    import torch
+    dev = torch.device("cuda", ctx.devices[0])
+    table = torch.zeros(modulus * nb, dtype=torch.int64, device=dev)
+    longest = max(e - s for s, e in w)
+    buf = torch.empty(longest, dtype=torch.uint8, device=dev)
+    idx = torch.arange(longest, dtype=torch.int64, device=dev)
+    for s, e in w:
+        u = ctx.unique_map(s, e, base, out=buf)[: e - s].to(torch.int64)
+        cls = (idx[: e - s] + s % modulus) % modulus
+        # (the next unique_map waits for this stream before it overwrites buf)
+        table += torch.bincount(cls * nb + u, minlength=modulus * nb)
+    return table.reshape(modulus, nb).tolist()
+
+
 # ranges per batched niceonly call (the library takes at most 2^20)
 NICEONLY_BATCH = 1 << 20
 

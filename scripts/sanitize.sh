@@ -31,6 +31,13 @@ ${CXX:-c++} -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover
     -I nice_amd/csrc tests/ranges_niceonly_san.cpp nice_amd/csrc/cpu_path.cpp -o nice_amd/build/asan/ranges_niceonly_san -lpthread
 ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
     nice_amd/build/asan/ranges_niceonly_san
+# The per-number map's host code likewise (the launch plan, fd2_map_plan.hpp, and
+# the CPU twin nice_cpu_unique_map): a program with its own main.
+echo "=== asan+ubsan: tests/map_san.cpp"
+${CXX:-c++} -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
+    -I nice_amd/csrc tests/map_san.cpp nice_amd/csrc/cpu_path.cpp -o nice_amd/build/asan/map_san -lpthread
+ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
+    nice_amd/build/asan/map_san
 # Canary: the ASan build must report a deliberate heap overflow (a 32-byte
 # histogram buffer where base 40 needs 41 u64 bins), or the runs above prove
 # nothing.
