@@ -224,6 +224,28 @@ def _pack_ranges(ranges):
     return (ctypes.c_uint64 * len(flat)).from_buffer_copy(flat), len(pairs)
 
 
+def _with_room(call, cap, bufs):
+    """call(*bufs(cap), cap, n_out) -> rc, again with the room it asks for while
+    it answers NICE_ERR_CAPACITY; returns (the buffers, n_out)."""
+    while True:
+        out, n = bufs(cap), ctypes.c_size_t()
+        rc = call(*out, cap, n)
+        if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
+            cap = n.value
+            continue
+        check(rc)
+        return out, n.value
+
+
+def _cpu_out(cap: int):
+    return (_lib.nice_number * max(cap, 1))()
+
+
+def _list_bufs(cap):
+    """A number list and its range indices."""
+    return _cpu_out(cap), (ctypes.c_uint32 * cap)()
+
+
 def _ranges_result(hist, nb, nrows, out, idx, n):
     full = memoryview(hist).cast("B").cast("Q").tolist()
     rows = [full[i * nb:(i + 1) * nb] for i in range(nrows)]
@@ -269,8 +291,9 @@ class GpuContext:
             pass
 
     def _out_buf(self, cap):
+        """The reused list buffer, as _with_room's buffers: a 1-tuple."""
         if cap > self._out_cap:
-            self._out = (_lib.nice_number * cap)()
+            self._out = ((_lib.nice_number * cap)(),)
             self._out_cap = cap
         return self._out
 
@@ -291,19 +314,10 @@ class GpuContext:
         hist = self._hist.get(base)
         if hist is None:
             hist = self._hist[base] = (ctypes.c_uint64 * (base + 1))()
-        cap = max(cap, self._out_cap, 1024)
-        while True:
-            out = self._out_buf(cap)
-            n = ctypes.c_size_t()
-            rc = lib().nice_process_range_detailed(self._h, *_split(start), *_split(end), base,
-                                                   hist, out, cap, n)
-            if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
-                cap = n.value
-                continue
-            check(rc)
-            lst = [(out[i].number_lo | (out[i].number_hi << 64), out[i].num_uniques)
-                   for i in range(n.value)]
-            return list(hist), lst
+        (out,), n = _with_room(lambda *a: lib().nice_process_range_detailed(
+            self._h, *_split(start), *_split(end), base, hist, *a), max(cap, self._out_cap, 1024), self._out_buf)
+        return list(hist), [(out[i].number_lo | (out[i].number_hi << 64), out[i].num_uniques)
+                            for i in range(n)]
 
     def detailed_submit(self, start: int, end: int, base: int) -> int:
         """Enqueue a detailed field and return at once (a ticket for
@@ -317,17 +331,10 @@ class GpuContext:
         hist = self._hist.get(base)
         if hist is None:
             hist = self._hist[base] = (ctypes.c_uint64 * (base + 1))()
-        cap = max(cap, self._out_cap, 1024)
-        while True:
-            out = self._out_buf(cap)
-            n = ctypes.c_size_t()
-            rc = lib().nice_detailed_collect(self._h, ticket, hist, out, cap, n)
-            if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
-                cap = n.value
-                continue
-            check(rc)
-            return list(hist), [(out[i].number_lo | (out[i].number_hi << 64), out[i].num_uniques)
-                                for i in range(n.value)]
+        (out,), n = _with_room(lambda *a: lib().nice_detailed_collect(self._h, ticket, hist, *a),
+                               max(cap, self._out_cap, 1024), self._out_buf)
+        return list(hist), [(out[i].number_lo | (out[i].number_hi << 64), out[i].num_uniques)
+                            for i in range(n)]
 
     # -- batched detailed ranges ------------------------------------------------
     def detailed_ranges(self, ranges, base: int, sum: bool = False, cap: int = 0):
@@ -341,16 +348,9 @@ class GpuContext:
         nb = base + 1
         hist = (ctypes.c_uint64 * (nb * (1 if sum else max(n_ranges, 1))))()
         flags = _lib.NICE_RANGES_SUM if sum else _lib.NICE_RANGES_PER_RANGE
-        cap = max(cap, 1024)
-        while True:
-            out, idx, n = _cpu_out(cap), (ctypes.c_uint32 * cap)(), ctypes.c_size_t()
-            rc = lib().nice_process_ranges_detailed(self._h, base, bounds, n_ranges, flags, hist, out, idx,
-                                                    cap, n)
-            if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
-                cap = n.value
-                continue
-            check(rc)
-            return _ranges_result(hist, nb, 1 if sum else n_ranges, out, idx, n.value)
+        (out, idx), n = _with_room(lambda *a: lib().nice_process_ranges_detailed(
+            self._h, base, bounds, n_ranges, flags, hist, *a), max(cap, 1024), _list_bufs)
+        return _ranges_result(hist, nb, 1 if sum else n_ranges, out, idx, n)
 
     def ranges_stats(self) -> "RangesStats":
         """Statistics of this context's last detailed_ranges call."""
@@ -440,18 +440,10 @@ class GpuContext:
         opts = self._nice_opts(msd_floor, chunk_size, threads, stride_k, msd_where, deal_stride,
                                deal_offset, filter)
         st = _lib.nice_niceonly_stats()
-        cap = max(cap, self._out_cap, 1024)
-        while True:
-            out = self._out_buf(cap)
-            n = ctypes.c_size_t()
-            rc = lib().nice_process_range_niceonly_ex(self._h, *_split(start), *_split(end), base,
-                                                      opts, out, cap, n, st)
-            if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
-                cap = n.value
-                continue
-            check(rc)
-            lst = [out[i].number_lo | (out[i].number_hi << 64) for i in range(n.value)]
-            return lst, _stats(st)
+        (out,), n = _with_room(lambda *a: lib().nice_process_range_niceonly_ex(
+            self._h, *_split(start), *_split(end), base, opts, *a, st),
+            max(cap, self._out_cap, 1024), self._out_buf)
+        return [out[i].number_lo | (out[i].number_hi << 64) for i in range(n)], _stats(st)
 
     @staticmethod
     def _nice_opts(msd_floor=0, chunk_size=0, threads=0, stride_k=0, msd_where="auto",
@@ -475,17 +467,9 @@ class GpuContext:
     def niceonly_collect(self, ticket: int, cap: int = 0):
         """(nice numbers, NiceonlyStats) of a submitted field."""
         st = _lib.nice_niceonly_stats()
-        cap = max(cap, self._out_cap, 1024)
-        while True:
-            out = self._out_buf(cap)
-            n = ctypes.c_size_t()
-            rc = lib().nice_niceonly_collect(self._h, ticket, out, cap, n, st)
-            if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
-                cap = n.value
-                continue
-            check(rc)
-            return ([out[i].number_lo | (out[i].number_hi << 64) for i in range(n.value)],
-                    _stats(st))
+        (out,), n = _with_room(lambda *a: lib().nice_niceonly_collect(self._h, ticket, *a, st),
+                               max(cap, self._out_cap, 1024), self._out_buf)
+        return [out[i].number_lo | (out[i].number_hi << 64) for i in range(n)], _stats(st)
 
     # -- both modes of one field ---------------------------------------------
     def both_raw(self, det_range, nice_range, base: int, **nice_opts):
@@ -662,29 +646,18 @@ def process_range_niceonly(range_: FieldSize, base: int,
                                       chunk_size=min(size, (1 << 64) - 1))
 
 
-def _cpu_out(cap: int):
-    return (_lib.nice_number * max(cap, 1))()
-
-
 def process_range_detailed_cpu(range_: FieldSize, base: int, threads: int = 1) -> FieldResults:
     """process_range_detailed (client_process.rs:150-191) on the host cores
     (nice_cpu_process_range_detailed): no device, for callers without a GPU.
     threads = 1 is the reference's single-threaded call."""
     hist = (ctypes.c_uint64 * (base + 1))()
-    cap = 1024
-    while True:
-        out, n = _cpu_out(cap), ctypes.c_size_t()
-        rc = lib().nice_cpu_process_range_detailed(*_split(range_.range_start), *_split(range_.range_end),
-                                                    base, threads, hist, out, cap, n)
-        if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
-            cap = n.value
-            continue
-        check(rc)
-        break
+    (out,), n = _with_room(lambda *a: lib().nice_cpu_process_range_detailed(
+        *_split(range_.range_start), *_split(range_.range_end), base, threads, hist, *a),
+        1024, lambda cap: (_cpu_out(cap),))
     return FieldResults(
         distribution=[UniquesDistributionSimple(i, hist[i]) for i in range(1, base + 1)],
         nice_numbers=[NiceNumberSimple(out[i].number_lo | (out[i].number_hi << 64), out[i].num_uniques)
-                      for i in range(n.value)])
+                      for i in range(n)])
 
 
 def unique_map_cpu(start: int, end: int, base: int, threads: int = 1):
@@ -703,16 +676,9 @@ def detailed_ranges_cpu(ranges, base: int, sum: bool = False, threads: int = 1):
     nb = base + 1
     hist = (ctypes.c_uint64 * (nb * (1 if sum else max(n_ranges, 1))))()
     flags = _lib.NICE_RANGES_SUM if sum else _lib.NICE_RANGES_PER_RANGE
-    cap = 1024
-    while True:
-        out, idx, n = _cpu_out(cap), (ctypes.c_uint32 * cap)(), ctypes.c_size_t()
-        rc = lib().nice_cpu_process_ranges_detailed(base, bounds, n_ranges, flags, threads, hist, out, idx,
-                                                     cap, n)
-        if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
-            cap = n.value
-            continue
-        check(rc)
-        return _ranges_result(hist, nb, 1 if sum else n_ranges, out, idx, n.value)
+    (out, idx), n = _with_room(lambda *a: lib().nice_cpu_process_ranges_detailed(
+        base, bounds, n_ranges, flags, threads, hist, *a), 1024, _list_bufs)
+    return _ranges_result(hist, nb, 1 if sum else n_ranges, out, idx, n)
 
 
 def _ranges_field_results(rows, lst, base: int) -> List[FieldResults]:
@@ -739,16 +705,9 @@ def _niceonly_ranges_call(call, n_ranges: int, cap: int):
     with room on NICE_ERR_CAPACITY."""
     cand = (ctypes.c_uint64 * max(n_ranges, 1))()
     sq = (ctypes.c_uint32 * max(n_ranges, 1))()
-    cap = max(cap, 1024)
-    while True:
-        out, idx, n = _cpu_out(cap), (ctypes.c_uint32 * cap)(), ctypes.c_size_t()
-        rc = call(cand, sq, out, idx, cap, n)
-        if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
-            cap = n.value
-            continue
-        check(rc)
-        return (list(cand[:n_ranges]), list(sq[:n_ranges]),
-                [(out[i].number_lo | (out[i].number_hi << 64), idx[i]) for i in range(n.value)])
+    (out, idx), n = _with_room(lambda *a: call(cand, sq, *a), max(cap, 1024), _list_bufs)
+    return (list(cand[:n_ranges]), list(sq[:n_ranges]),
+            [(out[i].number_lo | (out[i].number_hi << 64), idx[i]) for i in range(n)])
 
 
 def niceonly_ranges_cpu(ranges, base: int, stride_k: int = 0, threads: int = 1, cap: int = 0):
@@ -790,15 +749,8 @@ def process_range_niceonly_cpu(range_: FieldSize, base: int,
     stride table k from `stride_table` (default 2); filter="sound" runs the
     MSD recursion without Filter C."""
     k = stride_table.k if stride_table is not None else 2
-    cap = 256
-    while True:
-        out, n = _cpu_out(cap), ctypes.c_size_t()
-        rc = lib().nice_cpu_process_range_niceonly_ex(*_split(range_.range_start), *_split(range_.range_end),
-                                                       base, k, threads, _FILTERS[filter], out, cap, n)
-        if rc == _lib.NICE_ERR_CAPACITY and n.value > cap:  # retry only with more room
-            cap = n.value
-            continue
-        check(rc)
-        break
+    (out,), n = _with_room(lambda *a: lib().nice_cpu_process_range_niceonly_ex(
+        *_split(range_.range_start), *_split(range_.range_end), base, k, threads, _FILTERS[filter], *a),
+        256, lambda cap: (_cpu_out(cap),))
     return FieldResults(distribution=[], nice_numbers=[
-        NiceNumberSimple(out[i].number_lo | (out[i].number_hi << 64), base) for i in range(n.value)])
+        NiceNumberSimple(out[i].number_lo | (out[i].number_hi << 64), base) for i in range(n)])

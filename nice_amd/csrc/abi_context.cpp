@@ -36,15 +36,62 @@ int ensure_listbuf(Device &d, ListBuf &l, uint32_t cap, bool with_u) {
     return with_u ? grow_device(l.u, l.cap, cap, (size_t)cap * 4) : NICE_OK;
 }
 
+int read_list(const ListBuf &l, uint32_t cnt, std::vector<uint64_t> &n, std::vector<uint32_t> &u, hipStream_t s) {
+    n.resize((size_t)cnt * 2);
+    u.resize(cnt);
+    if (!cnt) return NICE_OK;
+    HIPCHK(hipMemcpyAsync(n.data(), l.n, (size_t)cnt * 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(u.data(), l.u, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
+    return NICE_OK;
+}
+
+int capacity_error(size_t n, size_t cap) {
+    return fail(NICE_ERR_CAPACITY,
+                "output list needs " + std::to_string(n) + " entries, capacity " + std::to_string(cap));
+}
+
+int check_ranges(const uint64_t *bounds, size_t n_ranges) {
+    for (size_t i = 0; i < n_ranges; i++)
+        if (!range_proper(bounds, i)) return fail(NICE_ERR_INVALID, range_refusal(i));
+    return NICE_OK;
+}
+
 int emit_list(std::vector<Entry> &all, nice_number *out, size_t cap, size_t *n_out) {
     std::sort(all.begin(), all.end(), [](const Entry &a, const Entry &b) { return a.n < b.n; });
     if (n_out) *n_out = all.size();
     const size_t c = std::min(cap, all.size());
     for (size_t i = 0; i < c; i++) put_entry(out[i], all[i]);
-    if (all.size() > cap)
-        return fail(NICE_ERR_CAPACITY, "output list needs " + std::to_string(all.size()) +
-                                           " entries, capacity " + std::to_string(cap));
+    return all.size() > cap ? capacity_error(all.size(), cap) : NICE_OK;
+}
+
+int SideStream::init(const Device &d) {
+    if (stream) return NICE_OK;
+    HIPCHK(hipSetDevice(d.id));
+    HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreate(&ev0));
+    HIPCHK(hipEventCreate(&ev1));
     return NICE_OK;
+}
+
+void SideStream::destroy(const Device &d) {
+    (void)hipSetDevice(d.id);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    (void)hipStreamDestroy(stream);
+}
+
+int StagePair::ensure(size_t units, size_t unit_bytes, hipStream_t busy) {
+    if (cap >= units) return NICE_OK;
+    const size_t c = std::max<size_t>(units, 4096);
+    if (busy) HIPCHK(hipStreamSynchronize(busy));
+    if (int rc = grow_pinned(h, cap, c, c * unit_bytes)) return rc;
+    return grow_device(d, cap, c, c * unit_bytes);
+}
+
+int KeptList::fits(size_t cap, size_t *n_out) {
+    if (n_out) *n_out = list.size();
+    kept = list.size() > cap;
+    return kept ? capacity_error(list.size(), cap) : NICE_OK;
 }
 
 int resolve_stats(Device &d) {

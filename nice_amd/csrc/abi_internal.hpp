@@ -199,68 +199,98 @@ struct NiceJob {
                                    // submitted (0: production); a re-run keeps it
 };
 
-// nice_process_ranges_detailed: one stream and its buffers per device, apart
-// from the slots (the call takes no detailed slot), and the last call's
-// results while the caller retries with a longer list.
-struct RangesDev {
+// The calls beside the field slots (batched detailed ranges, batched niceonly
+// ranges, the map) each keep, under a lock of their own (not ctx->mu: fields
+// in flight go on), per device a SideStream and the buffers below, and where
+// the caller may retry with a longer list the last call's results (KeptList).
+
+// A call's non-blocking stream on one device and the events around its launches.
+struct SideStream {
     hipStream_t stream = nullptr;
-    void *h_desc = nullptr, *d_desc = nullptr;  // pinned / device descriptors
-    size_t desc_cap = 0;                        // units
-    uint64_t *d_rows = nullptr;                 // histogram rows, then the list count
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    int init(const Device &d);  // on first use; leaves d current
+    // Wait for what was enqueued.
+    hipError_t drain(const Device &d) const { return (void)hipSetDevice(d.id), hipStreamSynchronize(stream); }
+    hipError_t elapsed(float *ms) const { return hipEventElapsedTime(ms, ev0, ev1); }
+    void destroy(const Device &d);  // after drain and the owner's buffers
+};
+
+// Pinned host staging and its device copy, of one capacity in units.
+struct StagePair {
+    void *h = nullptr, *d = nullptr;
+    size_t cap = 0;
+    // Room for `units` units (4096 at least), on the current device; `busy`:
+    // a stream whose queued work may still read the pair.
+    int ensure(size_t units, size_t unit_bytes, hipStream_t busy = nullptr);
+    void free() {
+        if (h) (void)hipHostFree(h);
+        if (d) (void)hipFree(d);
+    }
+};
+
+// What a batched call keeps after NICE_ERR_CAPACITY, for the same call with
+// room: the call (`key`: its flags or stride k) and its list; the owners add
+// their payload.
+struct KeptList {
+    bool kept = false;
+    uint32_t base = 0, key = 0;
+    std::vector<uint64_t> bounds;
+    std::vector<Entry> list;
+    bool holds(uint32_t b, uint32_t k, const uint64_t *bnd, size_t n_ranges) const {
+        return kept && base == b && key == k && bounds.size() == 4 * n_ranges &&
+               std::equal(bounds.begin(), bounds.end(), bnd);
+    }
+    void begin(uint32_t b, uint32_t k, const uint64_t *bnd, size_t n_ranges) {
+        kept = false, base = b, key = k, bounds.assign(bnd, bnd + 4 * n_ranges);
+    }
+    // *n_out = the list's length; NICE_ERR_CAPACITY, and the results kept,
+    // when it passes `cap`; else the caller copies the list out and drops it.
+    int fits(size_t cap, size_t *n_out);
+    void drop() { kept = false, bounds = {}, list = {}; }
+};
+
+struct RangesDev {
+    SideStream side;
+    StagePair desc;              // descriptors (kBatchDescBytes each)
+    uint64_t *d_rows = nullptr;  // histogram rows, then the list count
     size_t rows_cap = 0;
     uint32_t *d_count = nullptr;
     ListBuf list;
     uint32_t *chk_u = nullptr;  // self-check recompute of the listed numbers
     uint32_t chk_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
-struct RangesState {
+struct RangesState : KeptList {  // key: the flags
     std::vector<RangesDev> dev;
     nice_ranges_stats stats{};
-    // kept after NICE_ERR_CAPACITY, for the same call with room
-    bool kept = false;
-    uint32_t base = 0, flags = 0;
-    std::vector<uint64_t> bounds, hist;
-    std::vector<Entry> list;
+    std::vector<uint64_t> hist;
     std::vector<uint32_t> list_range;
 };
 
-// nice_process_ranges_niceonly: likewise one stream and its buffers per
-// device, apart from the niceonly slots -- its own copies of the residue
-// tables included (Device::residues belongs to fields, under ctx->mu) -- and
-// the last call's results while the caller retries with a longer list.
+// Its own copies of the residue tables included (Device::residues belongs to
+// fields, under ctx->mu).
 struct RangesNiceDev {
-    hipStream_t stream = nullptr;
-    RangeLeaf *h_leaves = nullptr, *d_leaves = nullptr;  // pinned / device leaf records
-    size_t leaf_cap = 0;
+    SideStream side;
+    StagePair leaves;          // RangeLeaf records
     uint32_t *d_sq = nullptr;  // square_ok, one counter per range
     size_t sq_cap = 0;
     uint32_t *d_ctl = nullptr;  // [0] the list count, then kDoneWords arrival counters
     uint32_t *h_count = nullptr, *d_count_mapped = nullptr;  // mapped: the list count at a launch's end
     ListBuf list;               // list.u: the entries' range indices
     std::map<uint32_t, uint32_t *> residues;  // base*8+k -> device residue table
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
-struct RangesNiceState {
+struct RangesNiceState : KeptList {  // key: the stride k; Entry::u: the range index
     std::vector<RangesNiceDev> dev;
     nice_ranges_niceonly_stats stats{};
-    // kept after NICE_ERR_CAPACITY, for the same call with room
-    bool kept = false;
-    uint32_t base = 0, k = 0, nice_min = 0;
-    std::vector<uint64_t> bounds, candidates;
+    uint32_t nice_min = 0;
+    std::vector<uint64_t> candidates;
     std::vector<uint32_t> square_ok;
-    std::vector<Entry> list;  // Entry::u: the range index
 };
 
-// nice_unique_map: likewise one stream and its buffers per device, apart from
-// the slots.
 struct MapDev {
-    hipStream_t stream = nullptr;
-    void *h_desc = nullptr, *d_desc = nullptr;  // pinned / device descriptors
-    size_t desc_cap = 0;                        // FD records
-    uint8_t *d_out = nullptr;                   // host mode: the device's shard of the map
+    SideStream side;
+    StagePair desc;             // FD records (kMapDescBytes each)
+    uint8_t *d_out = nullptr;   // host mode: the device's shard of the map
     size_t out_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 struct MapState {
     std::vector<MapDev> dev;
@@ -271,9 +301,9 @@ struct MapState {
 }  // namespace nice
 
 struct nice_ctx {
-    std::mutex map_mu;  // serialises nice_unique_map (not ctx->mu: fields in flight go on)
+    std::mutex map_mu;  // serialises nice_unique_map
     nice::abi::MapState map;
-    std::mutex ranges_mu;  // serialises nice_process_ranges_detailed (not ctx->mu: fields in flight go on)
+    std::mutex ranges_mu;  // ... nice_process_ranges_detailed
     nice::abi::RangesState ranges;
     std::mutex ranges_nice_mu;  // ... and nice_process_ranges_niceonly
     nice::abi::RangesNiceState ranges_nice;
@@ -378,7 +408,19 @@ int grow_pinned(T *&p, C &cap, C new_cap, size_t bytes) {
     return NICE_OK;
 }
 
+// After an error of a call beside the slots: wait for what it enqueued, on
+// every device (`dev`: its per-device blocks, one per device of the context).
+template <class Dev>
+void drain_all(const nice_ctx *ctx, const std::vector<Dev> &dev) {
+    for (size_t q = 0; q < dev.size(); q++)
+        if (dev[q].side.stream) (void)dev[q].side.drain(ctx->devs[q]);
+}
+
 int ensure_listbuf(Device &d, ListBuf &l, uint32_t cap, bool with_u);
+
+// Entries [0, cnt) of a device list into host vectors (n: (lo, hi) pairs),
+// async on `s`.
+int read_list(const ListBuf &l, uint32_t cnt, std::vector<uint64_t> &n, std::vector<uint32_t> &u, hipStream_t s);
 
 inline void put_entry(nice_number &o, const Entry &e) {
     o.number_lo = lo64(e.n);
@@ -386,6 +428,12 @@ inline void put_entry(nice_number &o, const Entry &e) {
     o.num_uniques = e.u;
     o.reserved = 0;
 }
+
+// NICE_ERR_CAPACITY for a list of n entries offered room for cap.
+int capacity_error(size_t n, size_t cap);
+
+// NICE_ERR_INVALID for the first range of `bounds` that is not range_proper.
+int check_ranges(const uint64_t *bounds, size_t n_ranges);
 
 // Sort `all` by n and hand it to the caller (NICE_ERR_CAPACITY: *n_out says
 // how many entries it needs).
@@ -515,11 +563,9 @@ inline hipError_t field_sync(const Slot &sl) {
 // possibly before the end-of-kernel event has completed).
 int resolve_stats(Device &d);
 
-// abi_ranges.cpp: a device's batch stream and buffers (nice_ctx_destroy).
+// A device's side stream and buffers (nice_ctx_destroy), each in its call's file.
 void ranges_dev_free(Device &d, RangesDev &r);
-// abi_ranges_niceonly.cpp: likewise.
 void ranges_nice_dev_free(Device &d, RangesNiceDev &r);
-// abi_map.cpp: likewise.
 void map_dev_free(Device &d, MapDev &r);
 
 }  // namespace abi

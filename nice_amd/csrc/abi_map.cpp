@@ -11,15 +11,6 @@ using nice::u128;
 
 namespace {
 
-int map_dev_init(Device &d, MapDev &r) {
-    if (r.stream) return NICE_OK;
-    HIPCHK(hipSetDevice(d.id));
-    HIPCHK(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&r.ev0));
-    HIPCHK(hipEventCreate(&r.ev1));
-    return NICE_OK;
-}
-
 // What the GPU call, its plan hook and (but for the context) the CPU twin
 // refuse; `size` out.
 int map_check_args(uint32_t base, u128 s, u128 e, const void *out, u128 &size) {
@@ -40,12 +31,7 @@ int map_enqueue(Device &d, MapDev &r, uint32_t base, const nice::MapBase &mb, u1
     nice::map_plan(mb, s, e, 0, pl);
     size_t nu = 0;
     for (const nice::MapRec &q : pl.recs) nu += q.kind == nice::kMapFd;
-    if (r.desc_cap < nu) {
-        const size_t c = std::max<size_t>(nu, 4096);
-        HIPCHK(hipStreamSynchronize(r.stream));
-        if (int rc = grow_pinned(r.h_desc, r.desc_cap, c, c * nice::kMapDescBytes)) return rc;
-        if (int rc = grow_device(r.d_desc, r.desc_cap, c, c * nice::kMapDescBytes)) return rc;
-    }
+    if (int rc = r.desc.ensure(nu, nice::kMapDescBytes, r.side.stream)) return rc;
     st.fd_segments += pl.fd_segments;
     st.generic_segments += pl.generic_segments;
     st.fd_numbers += pl.fd_numbers;
@@ -54,29 +40,25 @@ int map_enqueue(Device &d, MapDev &r, uint32_t base, const nice::MapBase &mb, u1
     p.base = base;
     p.recs = pl.recs.data();
     p.n_recs = pl.recs.size();
-    p.h_desc = r.h_desc;
-    p.d_desc = r.d_desc;
+    p.h_desc = r.desc.h;
+    p.d_desc = r.desc.d;
     p.out = out;
     p.launches = launches;
-    HIPCHK(hipEventRecord(r.ev0, r.stream));
-    const hipError_t err = nice::launch_unique_map(p, r.stream);
+    HIPCHK(hipEventRecord(r.side.ev0, r.side.stream));
+    const hipError_t err = nice::launch_unique_map(p, r.side.stream);
     if (err != hipSuccess) return fail(NICE_ERR_HIP, std::string("map launch: ") + hipGetErrorString(err));
-    HIPCHK(hipEventRecord(r.ev1, r.stream));
+    HIPCHK(hipEventRecord(r.side.ev1, r.side.stream));
     return NICE_OK;
 }
 
 }  // namespace
 
 void nice::abi::map_dev_free(Device &d, MapDev &r) {
-    if (!r.stream) return;
-    (void)hipSetDevice(d.id);
-    (void)hipStreamSynchronize(r.stream);
-    if (r.h_desc) (void)hipHostFree(r.h_desc);
-    if (r.d_desc) (void)hipFree(r.d_desc);
+    if (!r.side.stream) return;
+    (void)r.side.drain(d);
+    r.desc.free();
     if (r.d_out) (void)hipFree(r.d_out);
-    if (r.ev0) (void)hipEventDestroy(r.ev0);
-    if (r.ev1) (void)hipEventDestroy(r.ev1);
-    (void)hipStreamDestroy(r.stream);
+    r.side.destroy(d);
 }
 
 extern "C" {
@@ -146,33 +128,32 @@ int nice_unique_map(nice_ctx *ctx, uint64_t start_lo, uint64_t start_hi, uint64_
         const Shard &h = shards[enq];
         Device &d = ctx->devs[h.dv];
         MapDev &r = st.dev[h.dv];
-        rc = map_dev_init(d, r);
+        rc = r.side.init(d);
         uint8_t *dst = out;
         if (!rc && !in_place) {
             const size_t need = (size_t)(h.e - h.s);
             if (r.out_cap < need) {
                 (void)hipSetDevice(d.id);
-                rc = grow_device(r.d_out, r.out_cap, need, need, r.stream);
+                rc = grow_device(r.d_out, r.out_cap, need, need, r.side.stream);
             }
             dst = r.d_out;
         }
         if (!rc) rc = map_enqueue(d, r, base, mb, h.s, h.e, dst, st.stats, &launches[enq]);
         if (!rc && !in_place) {
             const hipError_t err = hipMemcpyAsync(out + (size_t)(h.s - s), r.d_out, (size_t)(h.e - h.s),
-                                                  hipMemcpyDeviceToHost, r.stream);
+                                                  hipMemcpyDeviceToHost, r.side.stream);
             if (err != hipSuccess) rc = fail(NICE_ERR_HIP, std::string("map copy: ") + hipGetErrorString(err));
         }
     }
     // wait for everything enqueued, also after an error
     for (size_t i = 0; i < enq; i++) {
         MapDev &r = st.dev[shards[i].dv];
-        if (!r.stream) continue;
-        (void)hipSetDevice(ctx->devs[shards[i].dv].id);
-        const hipError_t err = hipStreamSynchronize(r.stream);
+        if (!r.side.stream) continue;
+        const hipError_t err = r.side.drain(ctx->devs[shards[i].dv]);
         if (err != hipSuccess && !rc) rc = fail(NICE_ERR_HIP, std::string("map: ") + hipGetErrorString(err));
         if (rc) continue;
         float t = 0;
-        if (hipEventElapsedTime(&t, r.ev0, r.ev1) == hipSuccess) st.stats.kernel_ms = std::max(st.stats.kernel_ms, (double)t);
+        if (r.side.elapsed(&t) == hipSuccess) st.stats.kernel_ms = std::max(st.stats.kernel_ms, (double)t);
         st.stats.launches += launches[i];
     }
     return rc;

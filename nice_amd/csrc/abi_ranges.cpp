@@ -36,36 +36,19 @@ struct RangesCall {
     size_t n_ranges;
     bool sum;
     std::vector<std::vector<Entry>> per;  // the listed numbers of each range
-    void range(size_t i, u128 &s, u128 &e) const {
-        s = mk(bounds[4 * i], bounds[4 * i + 1]);
-        e = mk(bounds[4 * i + 2], bounds[4 * i + 3]);
-    }
 };
-
-int ranges_dev_init(Device &d, RangesDev &r) {
-    if (r.stream) return NICE_OK;
-    HIPCHK(hipSetDevice(d.id));
-    HIPCHK(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&r.ev0));
-    HIPCHK(hipEventCreate(&r.ev1));
-    return NICE_OK;
-}
 
 }  // namespace
 
 void nice::abi::ranges_dev_free(Device &d, RangesDev &r) {
-    if (!r.stream) return;
-    (void)hipSetDevice(d.id);
-    (void)hipStreamSynchronize(r.stream);
-    if (r.h_desc) (void)hipHostFree(r.h_desc);
-    if (r.d_desc) (void)hipFree(r.d_desc);
+    if (!r.side.stream) return;
+    (void)r.side.drain(d);
+    r.desc.free();
     if (r.d_rows) (void)hipFree(r.d_rows);
     if (r.list.n) (void)hipFree(r.list.n);
     if (r.list.u) (void)hipFree(r.list.u);
     if (r.chk_u) (void)hipFree(r.chk_u);
-    if (r.ev0) (void)hipEventDestroy(r.ev0);
-    if (r.ev1) (void)hipEventDestroy(r.ev1);
-    (void)hipStreamDestroy(r.stream);
+    r.side.destroy(d);
 }
 
 namespace {
@@ -75,11 +58,7 @@ int ranges_enqueue(Device &d, RangesDev &r, const Pass &p, uint32_t base, bool s
     HIPCHK(hipSetDevice(d.id));
     const size_t nu = p.units.size();
     const size_t nrows = sum ? kHistCopies : p.pr.size();
-    if (r.desc_cap < nu) {
-        const size_t c = std::max<size_t>(nu, 4096);
-        if (int rc = grow_pinned(r.h_desc, r.desc_cap, c, c * nice::kBatchDescBytes)) return rc;
-        if (int rc = grow_device(r.d_desc, r.desc_cap, c, c * nice::kBatchDescBytes)) return rc;
-    }
+    if (int rc = r.desc.ensure(nu, nice::kBatchDescBytes)) return rc;
     if (r.rows_cap < nrows) {
         const size_t c = std::max<size_t>(nrows, 1024);
         if (int rc = grow_device(r.d_rows, r.rows_cap, c, c * kHistBins * 8 + 16)) return rc;
@@ -87,23 +66,24 @@ int ranges_enqueue(Device &d, RangesDev &r, const Pass &p, uint32_t base, bool s
     }
     int rc = ensure_listbuf(d, r.list, std::max<uint32_t>(r.list.cap, 4096), true);
     if (rc) return rc;
-    HIPCHK(hipMemsetAsync(r.d_rows, 0, nrows * kHistBins * 8, r.stream));
-    HIPCHK(hipMemsetAsync(r.d_count, 0, 4, r.stream));
+    const hipStream_t stream = r.side.stream;
+    HIPCHK(hipMemsetAsync(r.d_rows, 0, nrows * kHistBins * 8, stream));
+    HIPCHK(hipMemsetAsync(r.d_count, 0, 4, stream));
     nice::BatchLaunch b{};
     b.base = base;
     b.cutoff = effective_cutoff(base);
     b.units = p.units.data();
     b.n_units = nu;
-    b.h_desc = r.h_desc;
-    b.d_desc = r.d_desc;
+    b.h_desc = r.desc.h;
+    b.d_desc = r.desc.d;
     b.hist = r.d_rows;
     b.ncopies = sum ? (uint32_t)kHistCopies : 0u;
     b.out = nice::NumOut{r.list.n, r.list.u, r.d_count, r.list.cap};
     b.launches = launches;
-    HIPCHK(hipEventRecord(r.ev0, r.stream));
-    const hipError_t err = nice::launch_detailed_fd2_batch(b, r.stream);
+    HIPCHK(hipEventRecord(r.side.ev0, stream));
+    const hipError_t err = nice::launch_detailed_fd2_batch(b, stream);
     if (err != hipSuccess) return fail(NICE_ERR_HIP, std::string("batch launch: ") + hipGetErrorString(err));
-    HIPCHK(hipEventRecord(r.ev1, r.stream));
+    HIPCHK(hipEventRecord(r.side.ev1, stream));
     return NICE_OK;
 }
 
@@ -113,10 +93,11 @@ int ranges_gather(Device &d, RangesDev &r, const Pass &p, uint32_t base, bool su
                   std::vector<uint64_t> &rows, std::vector<Entry> &list, double *ms) {
     HIPCHK(hipSetDevice(d.id));
     const size_t nrows = sum ? kHistCopies : p.pr.size();
+    const hipStream_t stream = r.side.stream;
     uint32_t cnt = 0;
     for (int attempt = 0;; attempt++) {
-        HIPCHK(hipMemcpyAsync(&cnt, r.d_count, 4, hipMemcpyDeviceToHost, r.stream));
-        HIPCHK(hipStreamSynchronize(r.stream));
+        HIPCHK(hipMemcpyAsync(&cnt, r.d_count, 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
         if (cnt <= r.list.cap) break;
         // the device list overflowed: grow it and run the pass again
         if (attempt) return fail(NICE_ERR_HIP, "near-miss list overflow after resize");
@@ -126,24 +107,23 @@ int ranges_gather(Device &d, RangesDev &r, const Pass &p, uint32_t base, bool su
         if (rc) return rc;
     }
     float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, r.ev0, r.ev1));
+    HIPCHK(r.side.elapsed(&t));
     *ms += t;
     rows.resize(nrows * kHistBins);
-    HIPCHK(hipMemcpyAsync(rows.data(), r.d_rows, nrows * kHistBins * 8, hipMemcpyDeviceToHost, r.stream));
+    HIPCHK(hipMemcpyAsync(rows.data(), r.d_rows, nrows * kHistBins * 8, hipMemcpyDeviceToHost, stream));
     list.clear();
     if (cnt) {
         if (r.chk_cap < cnt)
             if (int rc = grow_device(r.chk_u, r.chk_cap, r.list.cap, (size_t)r.list.cap * 4)) return rc;
         // self-check: every listed number's unique count recomputed by the
         // generic per-n device function
-        std::vector<uint64_t> nbuf((size_t)cnt * 2);
-        std::vector<uint32_t> ubuf(cnt), chk(cnt);
-        const hipError_t err = nice::launch_unique_counts(r.list.n, cnt, base, r.chk_u, r.stream);
+        std::vector<uint64_t> nbuf;
+        std::vector<uint32_t> ubuf, chk(cnt);
+        const hipError_t err = nice::launch_unique_counts(r.list.n, cnt, base, r.chk_u, stream);
         if (err != hipSuccess) return fail(NICE_ERR_HIP, std::string("self-check: ") + hipGetErrorString(err));
-        HIPCHK(hipMemcpyAsync(nbuf.data(), r.list.n, (size_t)cnt * 16, hipMemcpyDeviceToHost, r.stream));
-        HIPCHK(hipMemcpyAsync(ubuf.data(), r.list.u, (size_t)cnt * 4, hipMemcpyDeviceToHost, r.stream));
-        HIPCHK(hipMemcpyAsync(chk.data(), r.chk_u, (size_t)cnt * 4, hipMemcpyDeviceToHost, r.stream));
-        HIPCHK(hipStreamSynchronize(r.stream));
+        if (int rc = read_list(r.list, cnt, nbuf, ubuf, stream)) return rc;
+        HIPCHK(hipMemcpyAsync(chk.data(), r.chk_u, (size_t)cnt * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
         list.reserve(cnt);
         for (uint32_t q = 0; q < cnt; q++) {
             if (chk[q] != ubuf[q])
@@ -154,7 +134,7 @@ int ranges_gather(Device &d, RangesDev &r, const Pass &p, uint32_t base, bool su
         list.erase(std::unique(list.begin(), list.end(), [](const Entry &a, const Entry &b) { return a.n == b.n; }),
                    list.end());
     } else {
-        HIPCHK(hipStreamSynchronize(r.stream));
+        HIPCHK(hipStreamSynchronize(stream));
     }
     return NICE_OK;
 }
@@ -162,21 +142,13 @@ int ranges_gather(Device &d, RangesDev &r, const Pass &p, uint32_t base, bool su
 int ranges_emit(RangesState &st, uint64_t *hist, nice_number *out, uint32_t *out_range, size_t cap,
                 size_t *n_out) {
     std::memcpy(hist, st.hist.data(), st.hist.size() * 8);
-    const size_t n = st.list.size();
-    if (n_out) *n_out = n;
-    if (n > cap) {
-        st.kept = true;
-        return fail(NICE_ERR_CAPACITY,
-                    "output list needs " + std::to_string(n) + " entries, capacity " + std::to_string(cap));
-    }
-    for (size_t i = 0; i < n; i++) {
+    if (int rc = st.fits(cap, n_out)) return rc;
+    for (size_t i = 0; i < st.list.size(); i++) {
         put_entry(out[i], st.list[i]);
         if (out_range) out_range[i] = st.list_range[i];
     }
-    st.kept = false;
-    st.bounds = {};
+    st.drop();
     st.hist = {};
-    st.list = {};
     st.list_range = {};
     return NICE_OK;
 }
@@ -184,10 +156,7 @@ int ranges_emit(RangesState &st, uint64_t *hist, nice_number *out, uint32_t *out
 int ranges_check_args(uint32_t base, const uint64_t *bounds, size_t n_ranges) {
     if (base < 2 || base > 128) return fail(NICE_ERR_INVALID, "base must be in 2..=128");
     if (n_ranges == 0 || n_ranges > kRangesMax) return fail(NICE_ERR_INVALID, "n_ranges must be in 1..2^20");
-    for (size_t i = 0; i < n_ranges; i++)
-        if (mk(bounds[4 * i], bounds[4 * i + 1]) >= mk(bounds[4 * i + 2], bounds[4 * i + 3]))
-            return fail(NICE_ERR_INVALID, "range " + std::to_string(i) + " is empty or inverted");
-    return NICE_OK;
+    return check_ranges(bounds, n_ranges);
 }
 
 // Whether [s, e) runs in the batch: inside the valid range of an FD base.
@@ -206,8 +175,7 @@ std::vector<std::vector<Pass>> ranges_plan_passes(const RangesCall &c, const std
     u128 before = 0;
     std::vector<Pass> cur(nd);
     for (size_t i : batch) {
-        u128 s, e;
-        c.range(i, s, e);
+        const u128 s = nice::range_at(c.bounds, i, 0), e = nice::range_at(c.bounds, i, 1);
         size_t dv = batch_total ? (size_t)(before * nd / batch_total) : 0;
         if (dv >= nd) dv = nd - 1;
         before += e - s;
@@ -249,28 +217,15 @@ int ranges_run_rounds(nice_ctx *ctx, RangesState &st, RangesCall &c, const std::
         std::vector<uint32_t> launches(nd, 0);
         for (size_t dv = 0; dv < nd; dv++) {
             if (r >= passes[dv].size()) continue;
-            int rc = ranges_dev_init(ctx->devs[dv], st.dev[dv]);
+            int rc = st.dev[dv].side.init(ctx->devs[dv]);
             if (!rc) rc = ranges_enqueue(ctx->devs[dv], st.dev[dv], passes[dv][r], c.base, c.sum, &launches[dv]);
-            if (rc) {
-                for (size_t q = 0; q < dv; q++)  // drain what was enqueued
-                    if (r < passes[q].size()) (void)hipSetDevice(ctx->devs[q].id), (void)hipStreamSynchronize(st.dev[q].stream);
-                return rc;
-            }
+            if (rc) return drain_all(ctx, st.dev), rc;
         }
-        int first_rc = NICE_OK;
         for (size_t dv = 0; dv < nd; dv++) {
             if (r >= passes[dv].size()) continue;
             const Pass &p = passes[dv][r];
-            if (first_rc) {  // after an error: only wait for the other devices' passes
-                (void)hipSetDevice(ctx->devs[dv].id);
-                (void)hipStreamSynchronize(st.dev[dv].stream);
-                continue;
-            }
             int rc = ranges_gather(ctx->devs[dv], st.dev[dv], p, c.base, c.sum, &launches[dv], rows, list, &ms[dv]);
-            if (rc) {
-                first_rc = rc;
-                continue;
-            }
+            if (rc) return drain_all(ctx, st.dev), rc;  // the other devices' passes
             st.stats.launches += launches[dv];
             if (c.sum) {
                 for (size_t cp = 0; cp < kHistCopies; cp++)
@@ -286,7 +241,6 @@ int ranges_run_rounds(nice_ctx *ctx, RangesState &st, RangesCall &c, const std::
                 c.per[q.ri].insert(c.per[q.ri].end(), lo, hi);
             }
         }
-        if (first_rc) return first_rc;
     }
     for (double m : ms) st.stats.kernel_ms = std::max(st.stats.kernel_ms, m);
     return NICE_OK;
@@ -323,9 +277,8 @@ int ranges_assemble(RangesState &st, const RangesCall &c, u128 total) {
     st.list_range.clear();
     for (size_t i = 0; i < c.n_ranges; i++) {
         if (!c.sum) {
-            u128 s, e;
-            c.range(i, s, e);
-            int rc = validate_detailed(c.base, effective_cutoff(c.base), e - s, &st.hist[i * nb], c.per[i].size(),
+            const u128 size = nice::range_at(c.bounds, i, 1) - nice::range_at(c.bounds, i, 0);
+            int rc = validate_detailed(c.base, effective_cutoff(c.base), size, &st.hist[i * nb], c.per[i].size(),
                                        [&](size_t j) { return c.per[i][j]; });
             if (rc) return fail(rc, "range " + std::to_string(i) + ": " + nice_last_error());
         }
@@ -352,7 +305,7 @@ int nice_debug_ranges_plan(uint32_t base, const uint64_t *bounds, size_t n_range
     std::vector<nice::BatchUnit> v;
     size_t n = 0;
     for (size_t i = 0; i < n_ranges; i++) {
-        const u128 s = mk(bounds[4 * i], bounds[4 * i + 1]), e = mk(bounds[4 * i + 2], bounds[4 * i + 3]);
+        const u128 s = nice::range_at(bounds, i, 0), e = nice::range_at(bounds, i, 1);
         if (s < rs || e > re)
             return fail(NICE_ERR_INVALID, "range " + std::to_string(i) + " is not inside the base's valid range");
         v.clear();
@@ -384,23 +337,17 @@ int nice_process_ranges_detailed(nice_ctx *ctx, uint32_t base, const uint64_t *b
     if (int rc = ranges_check_args(base, bounds, n_ranges)) return rc;
     std::lock_guard<std::mutex> lock(ctx->ranges_mu);
     RangesState &st = ctx->ranges;
-    if (st.kept && st.base == base && st.flags == flags && st.bounds.size() == 4 * n_ranges &&
-        std::equal(st.bounds.begin(), st.bounds.end(), bounds))
-        return ranges_emit(st, hist, out, out_range, cap, n_out);
-    st.kept = false;
+    if (st.holds(base, flags, bounds, n_ranges)) return ranges_emit(st, hist, out, out_range, cap, n_out);
+    st.begin(base, flags, bounds, n_ranges);
     RangesCall c{base, bounds, n_ranges, flags == NICE_RANGES_SUM, std::vector<std::vector<Entry>>(n_ranges)};
     const size_t nb = base + 1, nd = ctx->devs.size();
     st.dev.resize(nd);
     st.stats = nice_ranges_stats{};
-    st.base = base;
-    st.flags = flags;
-    st.bounds.assign(bounds, bounds + 4 * n_ranges);
     st.hist.assign(c.sum ? nb : n_ranges * nb, 0);
     std::vector<size_t> batch, fallback;
     u128 total = 0, batch_total = 0;
     for (size_t i = 0; i < n_ranges; i++) {
-        u128 s, e;
-        c.range(i, s, e);
+        const u128 s = nice::range_at(c.bounds, i, 0), e = nice::range_at(c.bounds, i, 1);
         total += e - s;
         if (ranges_batchable(base, s, e)) batch.push_back(i), batch_total += e - s;
         else fallback.push_back(i);

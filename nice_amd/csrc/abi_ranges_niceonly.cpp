@@ -20,11 +20,8 @@ struct DevShare {
 };
 
 int ranges_nice_dev_init(Device &d, RangesNiceDev &r) {
-    if (r.stream) return NICE_OK;
-    HIPCHK(hipSetDevice(d.id));
-    HIPCHK(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&r.ev0));
-    HIPCHK(hipEventCreate(&r.ev1));
+    if (r.side.stream) return NICE_OK;
+    if (int rc = r.side.init(d)) return rc;
     HIPCHK(hipMalloc(&r.d_ctl, (1 + nice::kDoneWords) * 4));
     HIPCHK(hipHostMalloc(&r.h_count, 4, hipHostMallocMapped | hipHostMallocCoherent));
     *r.h_count = 0;
@@ -35,20 +32,16 @@ int ranges_nice_dev_init(Device &d, RangesNiceDev &r) {
 }  // namespace
 
 void nice::abi::ranges_nice_dev_free(Device &d, RangesNiceDev &r) {
-    if (!r.stream) return;
-    (void)hipSetDevice(d.id);
-    (void)hipStreamSynchronize(r.stream);
-    if (r.h_leaves) (void)hipHostFree(r.h_leaves);
-    if (r.d_leaves) (void)hipFree(r.d_leaves);
+    if (!r.side.stream) return;
+    (void)r.side.drain(d);
+    r.leaves.free();
     if (r.d_sq) (void)hipFree(r.d_sq);
     if (r.d_ctl) (void)hipFree(r.d_ctl);
     if (r.h_count) (void)hipHostFree(r.h_count);
     if (r.list.n) (void)hipFree(r.list.n);
     if (r.list.u) (void)hipFree(r.list.u);
     for (auto &kv : r.residues) (void)hipFree(kv.second);
-    if (r.ev0) (void)hipEventDestroy(r.ev0);
-    if (r.ev1) (void)hipEventDestroy(r.ev1);
-    (void)hipStreamDestroy(r.stream);
+    r.side.destroy(d);
 }
 
 namespace {
@@ -73,20 +66,17 @@ int ranges_nice_enqueue(Device &d, RangesNiceDev &r, const NiceRangesCall &c, co
         HIPCHK(hipMemcpy(p, c.table->residues.data(), c.table->residues.size() * 4, hipMemcpyHostToDevice));
     }
     const size_t nl = sh.leaves.size();
-    if (r.leaf_cap < nl) {
-        const size_t cap = std::max<size_t>(nl, 4096);
-        if (int rc = grow_pinned(r.h_leaves, r.leaf_cap, cap, cap * sizeof(nice::RangeLeaf))) return rc;
-        if (int rc = grow_device(r.d_leaves, r.leaf_cap, cap, cap * sizeof(nice::RangeLeaf))) return rc;
-    }
+    if (int rc = r.leaves.ensure(nl, sizeof(nice::RangeLeaf))) return rc;
     if (r.sq_cap < c.n_ranges) {
         const size_t cap = std::max<size_t>(c.n_ranges, 1024);
         if (int rc = grow_device(r.d_sq, r.sq_cap, cap, cap * 4)) return rc;
     }
     if (int rc = ensure_listbuf(d, r.list, std::max<uint32_t>(r.list.cap, 4096), true)) return rc;
-    std::memcpy(r.h_leaves, sh.leaves.data(), nl * sizeof(nice::RangeLeaf));
-    HIPCHK(hipMemcpyAsync(r.d_leaves, r.h_leaves, nl * sizeof(nice::RangeLeaf), hipMemcpyHostToDevice, r.stream));
-    HIPCHK(hipMemsetAsync(r.d_sq, 0, c.n_ranges * 4, r.stream));
-    HIPCHK(hipMemsetAsync(r.d_ctl, 0, (1 + nice::kDoneWords) * 4, r.stream));
+    const hipStream_t stream = r.side.stream;
+    std::memcpy(r.leaves.h, sh.leaves.data(), nl * sizeof(nice::RangeLeaf));
+    HIPCHK(hipMemcpyAsync(r.leaves.d, r.leaves.h, nl * sizeof(nice::RangeLeaf), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(r.d_sq, 0, c.n_ranges * 4, stream));
+    HIPCHK(hipMemsetAsync(r.d_ctl, 0, (1 + nice::kDoneWords) * 4, stream));
     *r.h_count = 0;
     nice::NiceRangesLaunch p{};
     p.c.residues = r.residues[key];
@@ -97,19 +87,19 @@ int ranges_nice_enqueue(Device &d, RangesNiceDev &r, const NiceRangesCall &c, co
     p.square_ok = r.d_sq;
     p.done = r.d_ctl + 1;
     p.count_mapped = r.d_count_mapped;
-    HIPCHK(hipEventRecord(r.ev0, r.stream));
+    HIPCHK(hipEventRecord(r.side.ev0, stream));
     for (int fast = 1; fast >= 0; fast--) {
-        p.leaves = r.d_leaves + (fast ? 0 : sh.n_fast);
+        p.leaves = (const nice::RangeLeaf *)r.leaves.d + (fast ? 0 : sh.n_fast);
         p.n_leaves = fast ? sh.n_fast : (uint32_t)(nl - sh.n_fast);
         if (!p.n_leaves) continue;
         p.c.in_range = (uint32_t)fast;
         p.c.nice_min = fast ? c.nice_min : c.base;
-        const hipError_t err = nice::launch_niceonly_ranges(p, d.num_cus, r.stream);
+        const hipError_t err = nice::launch_niceonly_ranges(p, d.num_cus, stream);
         if (err != hipSuccess)
             return fail(NICE_ERR_HIP, std::string("niceonly ranges launch: ") + hipGetErrorString(err));
         ++*launches;
     }
-    HIPCHK(hipEventRecord(r.ev1, r.stream));
+    HIPCHK(hipEventRecord(r.side.ev1, stream));
     return NICE_OK;
 }
 
@@ -118,9 +108,10 @@ int ranges_nice_enqueue(Device &d, RangesNiceDev &r, const NiceRangesCall &c, co
 int ranges_nice_gather(Device &d, RangesNiceDev &r, const NiceRangesCall &c, const DevShare &sh, uint32_t *launches,
                        std::vector<uint32_t> &square_ok, std::vector<Entry> &list, double *ms) {
     HIPCHK(hipSetDevice(d.id));
+    const hipStream_t stream = r.side.stream;
     uint32_t cnt = 0;
     for (int attempt = 0;; attempt++) {
-        HIPCHK(hipStreamSynchronize(r.stream));
+        HIPCHK(hipStreamSynchronize(stream));
         cnt = *r.h_count;  // published by the last launch's last workgroup
         if (cnt <= r.list.cap) break;
         // the device list overflowed: grow it and run the share again
@@ -132,17 +123,14 @@ int ranges_nice_gather(Device &d, RangesNiceDev &r, const NiceRangesCall &c, con
         if (rc) return rc;
     }
     float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, r.ev0, r.ev1));
+    HIPCHK(r.side.elapsed(&t));
     *ms = t;
     std::vector<uint32_t> sq(c.n_ranges);
-    HIPCHK(hipMemcpyAsync(sq.data(), r.d_sq, c.n_ranges * 4, hipMemcpyDeviceToHost, r.stream));
-    std::vector<uint64_t> nbuf((size_t)cnt * 2);
-    std::vector<uint32_t> ubuf(cnt);
-    if (cnt) {
-        HIPCHK(hipMemcpyAsync(nbuf.data(), r.list.n, (size_t)cnt * 16, hipMemcpyDeviceToHost, r.stream));
-        HIPCHK(hipMemcpyAsync(ubuf.data(), r.list.u, (size_t)cnt * 4, hipMemcpyDeviceToHost, r.stream));
-    }
-    HIPCHK(hipStreamSynchronize(r.stream));
+    HIPCHK(hipMemcpyAsync(sq.data(), r.d_sq, c.n_ranges * 4, hipMemcpyDeviceToHost, stream));
+    std::vector<uint64_t> nbuf;
+    std::vector<uint32_t> ubuf;
+    if (int rc = read_list(r.list, cnt, nbuf, ubuf, stream)) return rc;
+    HIPCHK(hipStreamSynchronize(stream));
     for (size_t i = 0; i < c.n_ranges; i++) square_ok[i] += sq[i];
     for (uint32_t q = 0; q < cnt; q++) {
         if (ubuf[q] >= c.n_ranges) return fail(NICE_ERR_HIP, "self-check: a listed number's range index is out of bounds");
@@ -155,22 +143,14 @@ int ranges_nice_emit(RangesNiceState &st, uint64_t *candidates, uint32_t *square
                      uint32_t *out_range, size_t cap, size_t *n_out) {
     if (candidates) std::memcpy(candidates, st.candidates.data(), st.candidates.size() * 8);
     if (square_ok) std::memcpy(square_ok, st.square_ok.data(), st.square_ok.size() * 4);
-    const size_t n = st.list.size();
-    if (n_out) *n_out = n;
-    if (n > cap) {
-        st.kept = true;
-        return fail(NICE_ERR_CAPACITY,
-                    "output list needs " + std::to_string(n) + " entries, capacity " + std::to_string(cap));
-    }
-    for (size_t i = 0; i < n; i++) {
+    if (int rc = st.fits(cap, n_out)) return rc;
+    for (size_t i = 0; i < st.list.size(); i++) {
         put_entry(out[i], Entry{st.list[i].n, st.base});  // num_uniques = base, like every niceonly entry
         if (out_range) out_range[i] = st.list[i].u;
     }
-    st.kept = false;
-    st.bounds = {};
+    st.drop();
     st.candidates = {};
     st.square_ok = {};
-    st.list = {};
     return NICE_OK;
 }
 
@@ -178,32 +158,18 @@ int ranges_nice_emit(RangesNiceState &st, uint64_t *candidates, uint32_t *square
 int ranges_nice_run(nice_ctx *ctx, RangesNiceState &st, const NiceRangesCall &c, const std::vector<DevShare> &shares) {
     const size_t nd = ctx->devs.size();
     std::vector<uint32_t> launches(nd, 0);
-    std::vector<char> queued(nd, 0);
-    auto drain = [&] {
-        for (size_t q = 0; q < nd; q++)
-            if (queued[q]) (void)hipSetDevice(ctx->devs[q].id), (void)hipStreamSynchronize(st.dev[q].stream);
-    };
     for (size_t dv = 0; dv < nd; dv++) {
         if (shares[dv].leaves.empty()) continue;
         int rc = ranges_nice_dev_init(ctx->devs[dv], st.dev[dv]);
-        if (!rc) {
-            queued[dv] = 1;
-            rc = ranges_nice_enqueue(ctx->devs[dv], st.dev[dv], c, shares[dv], &launches[dv]);
-        }
-        if (rc) {
-            drain();
-            return rc;
-        }
+        if (!rc) rc = ranges_nice_enqueue(ctx->devs[dv], st.dev[dv], c, shares[dv], &launches[dv]);
+        if (rc) return drain_all(ctx, st.dev), rc;
     }
     for (size_t dv = 0; dv < nd; dv++) {
-        if (!queued[dv]) continue;
+        if (shares[dv].leaves.empty()) continue;
         double ms = 0;
         const int rc = ranges_nice_gather(ctx->devs[dv], st.dev[dv], c, shares[dv], &launches[dv], st.square_ok,
                                           st.list, &ms);
-        if (rc) {
-            drain();
-            return rc;
-        }
+        if (rc) return drain_all(ctx, st.dev), rc;
         st.stats.launches += launches[dv];
         st.stats.kernel_ms = std::max(st.stats.kernel_ms, ms);
     }
@@ -248,24 +214,18 @@ int nice_process_ranges_niceonly(nice_ctx *ctx, uint32_t base, const uint64_t *b
     if (!ctx || !bounds || (cap && !out)) return fail(NICE_ERR_INVALID, "null argument");
     const uint32_t k = stride_k ? stride_k : 2;
     if (const char *why = nice::nice_ranges_check(base, n_ranges, k)) return fail(NICE_ERR_INVALID, why);
-    for (size_t i = 0; i < n_ranges; i++)
-        if (nice::range_at(bounds, i, 0) >= nice::range_at(bounds, i, 1))
-            return fail(NICE_ERR_INVALID, "range " + std::to_string(i) + " is empty or inverted");
+    if (int rc = check_ranges(bounds, n_ranges)) return rc;
     std::lock_guard<std::mutex> lock(ctx->ranges_nice_mu);
     RangesNiceState &st = ctx->ranges_nice;
-    if (st.kept && st.base == base && st.k == k && st.bounds.size() == 4 * n_ranges &&
-        std::equal(st.bounds.begin(), st.bounds.end(), bounds))
+    if (st.holds(base, k, bounds, n_ranges))
         return ranges_nice_emit(st, candidates, square_ok, out, out_range, cap, n_out);
-    st.kept = false;
+    st.begin(base, k, bounds, n_ranges);
     const size_t nd = ctx->devs.size();
     st.dev.resize(nd);
     st.stats = nice_ranges_niceonly_stats{};
-    st.base = base;
-    st.k = k;
     // as a field submitted now would take it: in range, the compile-time kernels
     const uint32_t hook = g_nice_min_override[base].load(std::memory_order_relaxed);
     st.nice_min = hook ? hook : base;
-    st.bounds.assign(bounds, bounds + 4 * n_ranges);
     st.candidates.assign(n_ranges, 0);
     st.square_ok.assign(n_ranges, 0);
     st.list.clear();

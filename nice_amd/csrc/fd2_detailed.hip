@@ -233,15 +233,25 @@ void fd2_batch_plan(uint32_t base, u128 a, u128 e, uint32_t row, std::vector<Bat
     }
 }
 
+namespace fd2 {
+// Whether the batch-configuration kernels' (batch, map) init_at reads a
+// descriptor's xs: only where n passes 64 bits and the kernel keeps 32-bit
+// init columns (Cfg::N64, C64).
+static bool unit_reads_digits(uint32_t base) {
+    return fd2_supported(base) && !fits64(base, digits_of((int)base).dn) && fd2_batch_wg(base) < 1024;
+}
+// A descriptor's xs: zeros, or (`read`) the radix-b^2 digits of its first n.
+static void unit_digits(uint32_t base, bool read, u64 lo, u64 hi, u32 *xs) {
+    for (int k = 0; k < kXDigits; k++) xs[k] = 0;
+    if (read) host_digits(((u128)hi << 64) | lo, base * base, xs, cdiv(digits_of((int)base).dn, 2));  // Cfg::B, NX
+}
+}  // namespace fd2
+
 hipError_t launch_detailed_fd2_batch(const BatchLaunch &p, hipStream_t s) {
     if (!fd2_supported(p.base) || !p.n_units || p.n_units > 0x7fffffffull) return hipErrorInvalidValue;
     const fd2::BaseThresholds &t = fd2::thresholds(p.base);
     const size_t nc = t.combos.size();
-    const u32 B = p.base * p.base;
-    const int dn = fd2::digits_of((int)p.base).dn, nx = cdiv(dn, 2);  // Cfg::DN, NX
-    // init_at reads the digits only where n passes 64 bits and the kernel
-    // keeps 32-bit init columns (Cfg::N64, C64)
-    const bool digits = !fd2::fits64(p.base, dn) && fd2_batch_wg(p.base) < 1024;
+    const bool digits = fd2::unit_reads_digits(p.base);
     // descriptors grouped by combo (a counting sort: the order within a combo
     // is the plan's, ascending n within a range)
     std::vector<size_t> first(nc + 1, 0);
@@ -262,8 +272,7 @@ hipError_t launch_detailed_fd2_batch(const BatchLaunch &p, hipStream_t s) {
         d.chunk = u.chunk;
         d.row = u.row;
         d.pad = 0;
-        for (int k = 0; k < fd2::kXDigits; k++) d.xs[k] = 0;
-        if (digits) fd2::host_digits(((u128)u.hi << 64) | u.lo, B, d.xs, nx);
+        fd2::unit_digits(p.base, digits, u.lo, u.hi, d.xs);
     }
     hipError_t err = hipMemcpyAsync(p.d_desc, p.h_desc, p.n_units * kBatchDescBytes, hipMemcpyHostToDevice, s);
     if (err != hipSuccess) return err;
@@ -313,11 +322,7 @@ MapBase map_base(uint32_t base) {
 hipError_t launch_unique_map(const MapLaunch &p, hipStream_t s) {
     const bool fd = fd2_supported(p.base);
     const fd2::BaseThresholds *t = fd ? &fd2::thresholds(p.base) : nullptr;
-    const u32 B = p.base * p.base;
-    const int dn = fd2::digits_of((int)p.base).dn, nx = cdiv(dn, 2);  // Cfg::DN, NX
-    // init_at reads the digits only where n passes 64 bits and the kernel
-    // keeps 32-bit init columns (Cfg::N64, C64)
-    const bool digits = fd && !fd2::fits64(p.base, dn) && fd2_batch_wg(p.base) < 1024;
+    const bool digits = fd2::unit_reads_digits(p.base);
     fd2::Fd2MapUnit *h = (fd2::Fd2MapUnit *)p.h_desc;
     static_assert(sizeof(fd2::Fd2MapUnit) == kMapDescBytes, "descriptor size");
     size_t nu = 0;
@@ -331,8 +336,7 @@ hipError_t launch_unique_map(const MapLaunch &p, hipStream_t s) {
         d.off = r.off;
         d.lanes = r.lanes;
         d.chunk = r.chunk;
-        for (int k = 0; k < fd2::kXDigits; k++) d.xs[k] = 0;
-        if (digits) fd2::host_digits(((u128)r.hi << 64) | r.lo, B, d.xs, nx);
+        fd2::unit_digits(p.base, digits, r.lo, r.hi, d.xs);
     }
     hipError_t err;
     if (nu && (err = hipMemcpyAsync(p.d_desc, p.h_desc, nu * kMapDescBytes, hipMemcpyHostToDevice, s)) != hipSuccess)

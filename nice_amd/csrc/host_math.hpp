@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cmath>
 #include <memory>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -458,5 +459,18 @@ inline u128 client_chunk_size(u128 size) {
     mult = std::max<u128>(1, std::min<u128>(mult, 1000));
     return def * mult;
 }
+
+// The batched calls' `bounds` (four u64 per range: start lo, hi, end lo, hi):
+// range i's start (end = 0) or end (1) ...
+inline u128 range_at(const uint64_t *bounds, size_t i, int end) {
+    return ((u128)bounds[4 * i + 2 * end + 1] << 64) | bounds[4 * i + 2 * end];
+}
+
+// ... whether a call takes it (the check runs per range of calls with 10^5
+// ranges: it builds no string) ...
+inline bool range_proper(const uint64_t *bounds, size_t i) { return range_at(bounds, i, 0) < range_at(bounds, i, 1); }
+
+// ... and what the call says of one it does not take.
+inline std::string range_refusal(size_t i) { return "range " + std::to_string(i) + " is empty or inverted"; }
 
 }  // namespace nice

@@ -71,10 +71,6 @@ inline const char *nice_ranges_check(uint32_t base, size_t n_ranges, uint32_t k)
     return nullptr;
 }
 
-inline u128 range_at(const uint64_t *bounds, size_t i, int end) {
-    return ((u128)bounds[4 * i + 2 * end + 1] << 64) | bounds[4 * i + 2 * end];
-}
-
 // Whether [s, e) runs the compile-time kernel of `base` on the k table.
 inline bool nice_range_fast(uint32_t base, uint32_t k, u128 s, u128 e) {
     if (k != 2 || !niceonly_fast_base(base)) return false;
@@ -126,8 +122,8 @@ inline NiceRangesPlan plan_nice_ranges(uint32_t base, uint32_t k, const StrideTa
     size_t n_leaves = 0;
     for (size_t i = 0; i < n_ranges; i++) {
         const u128 s = range_at(bounds, i, 0), e = range_at(bounds, i, 1);
-        if (s >= e) {
-            pl.error = "range " + std::to_string(i) + " is empty or inverted";
+        if (!range_proper(bounds, i)) {
+            pl.error = range_refusal(i);
             return pl;
         }
         const u128 c = t.index_of(e) - t.index_of(s);

@@ -11,7 +11,7 @@ import random
 import pytest
 
 import nice_amd as N
-from nice_amd import _lib, survey
+from nice_amd import _lib, api, survey
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -288,6 +288,22 @@ def test_device_list_overflow_reruns_the_batch(near):
         assert srow == [[5000 * v for v in rows[0]]] and slst == lst
     finally:
         c.close()
+
+
+def test_descriptor_staging_regrows_between_calls(ctx):
+    """One context, three calls: 1 range, then 5000 ranges of 100 numbers --
+    more workgroups than the descriptor staging's first size (4096), so the
+    pinned and device buffers are replaced -- then 1 range again, each against
+    the CPU twin."""
+    s, e = O.base_range(40)
+    rng = random.Random(11)
+    big = [(a, a + 100) for a in sorted(rng.sample(range(s, e - 1000, 1000), 5000))]
+    units = ctypes.c_size_t()
+    _lib.check(_lib.lib().nice_debug_ranges_plan(40, api._pack_ranges(big)[0], len(big), None, 0, units))
+    assert units.value > 4096
+    for ranges in ([big[0]], big, [big[-1]]):
+        assert ctx.detailed_ranges(ranges, 40) == api.detailed_ranges_cpu(ranges, 40, threads=16)
+        assert ctx.ranges_stats().fallback_ranges == 0
 
 
 # --- 7. two devices ------------------------------------------------------------------------------

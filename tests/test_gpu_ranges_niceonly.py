@@ -262,6 +262,23 @@ def test_list_overflow_keeps_the_results(ctx):
         c2.close()
 
 
+def test_leaf_staging_regrows_between_calls(ctx):
+    """One context, three calls: 1 range, then 5000 ranges of 10^4 numbers --
+    more leaf records than the leaf staging's first size (4096), so the pinned
+    and device buffers are replaced -- then 1 range again, each against the CPU
+    twin (all in range on the k = 2 table: square_ok counted on both sides)."""
+    s, e = O.base_range(40)
+    rng = random.Random(12)
+    big = [(a, a + 10 ** 4) for a in sorted(rng.sample(range(s, e - 10 ** 5, 10 ** 5), 5000))]
+    leaves = ctypes.c_size_t()
+    _lib.check(_lib.lib().nice_debug_ranges_niceonly_plan(40, 0, api._pack_ranges(big)[0], len(big), 1, None, 0,
+                                                          leaves))
+    assert leaves.value > 4096
+    for ranges in ([big[0]], big, [big[-1]]):
+        assert ctx.niceonly_ranges(ranges, 40) == N.niceonly_ranges_cpu(ranges, 40, threads=THREADS)
+        assert ctx.ranges_niceonly_stats().generic_ranges == 0
+
+
 # --- beside fields in flight --------------------------------------------------------------------------
 def test_independent_of_fields_in_flight(ctx):
     s, _ = O.base_range(40)
