@@ -576,6 +576,69 @@ int nice_last_map_stats(nice_ctx *ctx, nice_map_stats *out);
 int nice_debug_map_plan(uint32_t base, uint64_t start_lo, uint64_t start_hi, uint64_t end_lo,
                         uint64_t end_hi, uint64_t *records, size_t cap, size_t *n_out);
 
+/* The device MSD recursion's range list: what nice_msd_valid_ranges_ex returns,
+ * for many roots per call, at device speed.  `roots` holds four u64 per root
+ * -- start_lo, start_hi, end_lo, end_hi, the layout every ranges call uses.
+ * Root i is one recursion root (depth 0, depth cap 22, factor 2): its answer is
+ * exactly nice_msd_valid_ranges_ex(root i, base, floor_size, filter).  `out`
+ * receives the concatenation of the roots' answers in root order, each root's
+ * ranges ascending, as quadruples in the same layout, so it can be passed
+ * unchanged as the `bounds` of nice_process_ranges_niceonly or
+ * nice_process_ranges_detailed.  out_root[j] (may be null) is entry j's root
+ * index, counts[i] (may be null) the number of ranges of root i.  Roots may
+ * overlap or repeat: each gets its own complete answer.
+ * The kernels run the node rule of the field kernels (classify_node with the
+ * field kernels' template arguments for the base and the root's placement), so
+ * the roots of a field's chunk grid give the ranges that field's niceonly run
+ * tests.  filter: NICE_FILTER_REFERENCE or NICE_FILTER_SOUND; the sound filter
+ * only leaves Filter C out of the recursion -- its per-candidate prefix test
+ * is not part of a range list.
+ * Roots of at most kFusedMaxCap - 2 floors run one workgroup per root, larger
+ * ones a level BFS; the records are ordered on the device and only the ones
+ * written are copied back.  On a context of several devices the roots are dealt
+ * in contiguous runs balanced by numbers.  Buffers are sized from the bound of
+ * size / floor_size + 1 leaves per root (2^22 at most, the depth cap), and a
+ * call is cut into batches of roots of 2^27 such nodes (64 bytes of device
+ * memory each, allocated as a call needs them): no valid call ends in
+ * NICE_ERR_MSD_OVERFLOW.
+ * Errors: NICE_ERR_INVALID (n_roots 0 or above 2^20; an empty or inverted
+ * root -- the message names its index --; a root of more than 2^40 numbers;
+ * floor_size 0; a filter other than the two; a base outside 2..128),
+ * NICE_ERR_CAPACITY (*n_out = the needed length; the results are kept, and
+ * the same call with room returns them without running again).
+ * The call has its own stream, buffers and lock per device: it takes no
+ * niceonly slot and does not wait for fields in flight. */
+int nice_msd_ranges(nice_ctx *ctx, uint32_t base, const uint64_t *roots, size_t n_roots,
+                    uint64_t floor_size, uint32_t filter, uint64_t *out, uint32_t *out_root,
+                    uint64_t *counts, size_t cap, size_t *n_out);
+/* The same on the host cores (no device): the host recursion root by root, the
+ * roots spread over `threads`.  The same outputs and errors. */
+int nice_cpu_msd_ranges(uint32_t base, const uint64_t *roots, size_t n_roots, uint64_t floor_size,
+                        uint32_t filter, int32_t threads, uint64_t *out, uint32_t *out_root,
+                        uint64_t *counts, size_t cap, size_t *n_out);
+typedef struct {
+    uint32_t launches;    /* recursion kernel launches of the last call that ran (level-0 and level
+                             launches and the workgroup-per-root launches; the sort's are not counted;
+                             a retry after NICE_ERR_CAPACITY returns kept results and leaves the
+                             statistics) */
+    uint32_t fused_roots; /* roots run one workgroup per root */
+    uint32_t level_roots; /* roots run by the level BFS */
+    uint32_t reserved;
+    uint64_t ranges;      /* summed over the roots */
+    uint64_t numbers;     /* the numbers inside them */
+    double kernel_ms;     /* HIP events around the recursion launches, summed over the batches
+                             (the slowest device) */
+    double order_ms;      /* ... and around the device sort of the records */
+} nice_msd_ranges_stats;
+int nice_last_msd_ranges_stats(nice_ctx *ctx, nice_msd_ranges_stats *out);
+/* Test hook (no device): the plan of nice_msd_ranges on a context of n_devices
+ * devices.  Writes 4 u64 per root, in root order: root index, group (1: one
+ * workgroup per root, 0: the level BFS), device, batch (counted per device).
+ * *n_out = the true count.  The argument errors of nice_msd_ranges. */
+int nice_debug_msd_ranges_plan(uint32_t base, const uint64_t *roots, size_t n_roots,
+                               uint64_t floor_size, uint32_t n_devices, uint64_t *records,
+                               size_t cap, size_t *n_out);
+
 /* Diagnostics: per-n results of the device functions the kernels use. */
 int nice_debug_unique_counts(nice_ctx *ctx, const uint64_t *n_pairs, uint32_t count,
                              uint32_t base, uint32_t *out);

@@ -57,6 +57,7 @@ EXPORTS = (
     "nice_process_ranges_niceonly", "nice_last_ranges_niceonly_stats", "nice_cpu_process_ranges_niceonly",
     "nice_debug_ranges_niceonly_plan",
     "nice_unique_map", "nice_cpu_unique_map", "nice_last_map_stats", "nice_debug_map_plan",
+    "nice_msd_ranges", "nice_cpu_msd_ranges", "nice_last_msd_ranges_stats", "nice_debug_msd_ranges_plan",
 )
 
 
@@ -114,6 +115,13 @@ class nice_map_stats(ctypes.Structure):
                 ("generic_segments", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("fd_numbers", ctypes.c_uint64), ("generic_numbers", ctypes.c_uint64),
                 ("kernel_ms", ctypes.c_double)]
+
+
+class nice_msd_ranges_stats(ctypes.Structure):
+    _fields_ = [("launches", ctypes.c_uint32), ("fused_roots", ctypes.c_uint32),
+                ("level_roots", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("ranges", ctypes.c_uint64), ("numbers", ctypes.c_uint64),
+                ("kernel_ms", ctypes.c_double), ("order_ms", ctypes.c_double)]
 
 
 _lib = None
@@ -207,6 +215,10 @@ def lib():
         "nice_cpu_unique_map": ([u64, u64, u64, u64, u32, i32, vp, sz], i32),
         "nice_last_map_stats": ([vp, ctypes.POINTER(nice_map_stats)], i32),
         "nice_debug_map_plan": ([u32, u64, u64, u64, u64, P64, sz, PSZ], i32),
+        "nice_msd_ranges": ([vp, u32, P64, sz, u64, u32, P64, P32, P64, sz, PSZ], i32),
+        "nice_cpu_msd_ranges": ([u32, P64, sz, u64, u32, i32, P64, P32, P64, sz, PSZ], i32),
+        "nice_last_msd_ranges_stats": ([vp, ctypes.POINTER(nice_msd_ranges_stats)], i32),
+        "nice_debug_msd_ranges_plan": ([u32, P64, sz, u64, u32, P64, sz, PSZ], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -204,9 +204,72 @@ class RangesNiceonlyStats:
     kernel_ms: float     # HIP events around the launches (the slowest device)
 
 
+@dataclass
+class MsdRangesStats:
+    launches: int     # recursion kernel launches of the call (the sort's not counted)
+    fused_roots: int  # roots run one workgroup per root
+    level_roots: int  # roots run by the level BFS
+    ranges: int       # summed over the roots
+    numbers: int      # the numbers inside them
+    kernel_ms: float  # HIP events around the recursion launches (the slowest device)
+    order_ms: float   # ... and around the device sort of the records
+
+
+class RangeBounds:
+    """A range list as the library holds it: four u64 per range (start_lo,
+    start_hi, end_lo, end_hi), what msd_ranges returns.  niceonly_ranges,
+    detailed_ranges and msd_ranges take it as it is, with no loop over the
+    ranges; indexing and iteration give (start, end) pairs."""
+
+    def __init__(self, buf, n: int, roots=None):
+        self.buf, self.n = buf, n
+        self.roots = roots  # per range, the index of the root it came from (msd_ranges), or None
+
+    def __len__(self):
+        return self.n
+
+    def _words(self):
+        return memoryview(self.buf).cast("B").cast("Q")[:4 * self.n].tolist()
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return self.tolist()[i]
+        if i < 0:
+            i += self.n
+        if not 0 <= i < self.n:
+            raise IndexError(i)
+        b = self.buf
+        return (b[4 * i] | (b[4 * i + 1] << 64), b[4 * i + 2] | (b[4 * i + 3] << 64))
+
+    def __iter__(self):
+        return iter(self.tolist())
+
+    def tolist(self):
+        w = self._words()
+        return [(w[i] | (w[i + 1] << 64), w[i + 2] | (w[i + 3] << 64)) for i in range(0, len(w), 4)]
+
+    def part(self, i: int, j: int) -> "RangeBounds":
+        """Ranges [i, j) as a RangeBounds of their own (one buffer copy)."""
+        i, j = max(0, min(i, self.n)), max(0, min(j, self.n))
+        raw = memoryview(self.buf).cast("B")[32 * i:32 * max(i, j)]
+        buf = (ctypes.c_uint64 * max(4 * (j - i), 4))()
+        ctypes.memmove(buf, bytes(raw), len(raw))
+        return RangeBounds(buf, max(0, j - i), self.roots[i:j] if self.roots is not None else None)
+
+    def root_list(self):
+        return list(self.roots[:self.n]) if self.roots is not None else None
+
+    def numbers(self) -> int:
+        """The numbers inside the ranges, summed."""
+        w = self._words()
+        return sum(w[2::4]) - sum(w[0::4]) + ((sum(w[3::4]) - sum(w[1::4])) << 64)
+
+
 def _pack_ranges(ranges):
     """(start, end) pairs or FieldSize -> the four-u64-per-range bounds array
-    nice_msd_valid_ranges writes."""
+    nice_msd_valid_ranges writes (a RangeBounds is that array already)."""
+    if isinstance(ranges, RangeBounds):
+        return ranges.buf, len(ranges)
     pairs = [(r.range_start, r.range_end) if isinstance(r, FieldSize) else (int(r[0]), int(r[1]))
              for r in ranges]
     if any(s < 0 or e < 0 or s >> 128 or e >> 128 for s, e in pairs):
@@ -423,6 +486,29 @@ class GpuContext:
         check(lib().nice_last_ranges_niceonly_stats(self._h, s))
         return RangesNiceonlyStats(s.launches, s.fast_ranges, s.generic_ranges, s.candidates, s.square_ok,
                                    s.kernel_ms)
+
+    # -- the device MSD recursion's range list ----------------------------------
+    def msd_ranges(self, roots, base: int, floor_size: int = 250, filter: str = "reference", cap: int = 0):
+        """The MSD recursion's surviving ranges of many roots in one call
+        (nice_msd_ranges): `roots` holds (start, end) pairs, FieldSize or a
+        RangeBounds, e.g. chunk_roots(start, end, chunk) -- then the list is
+        the one that field's niceonly run tests.  Each root's answer is
+        get_valid_ranges(root, base, floor_size, filter).  Returns (bounds,
+        counts): a RangeBounds (the roots' answers concatenated in root order,
+        bounds.roots the root index per range) that niceonly_ranges and
+        detailed_ranges take unchanged, and the number of ranges per root.
+        See msd_ranges_stats()."""
+        rb, n_roots = _pack_ranges(roots)
+        return _msd_ranges_call(
+            lambda *a: lib().nice_msd_ranges(self._h, base, rb, n_roots, floor_size, _FILTERS[filter], *a),
+            n_roots, cap)
+
+    def msd_ranges_stats(self) -> "MsdRangesStats":
+        """Statistics of this context's last msd_ranges call."""
+        s = _lib.nice_msd_ranges_stats()
+        check(lib().nice_last_msd_ranges_stats(self._h, s))
+        return MsdRangesStats(s.launches, s.fused_roots, s.level_roots, s.ranges, s.numbers, s.kernel_ms,
+                              s.order_ms)
 
     # -- niceonly -------------------------------------------------------------
     def niceonly_raw(self, start: int, end: int, base: int, msd_floor: int = 0,
@@ -718,6 +804,58 @@ def niceonly_ranges_cpu(ranges, base: int, stride_k: int = 0, threads: int = 1, 
     return _niceonly_ranges_call(
         lambda *a: lib().nice_cpu_process_ranges_niceonly(base, bounds, n_ranges, stride_k, threads, *a),
         n_ranges, cap)
+
+
+def _msd_ranges_call(call, n_roots: int, cap: int):
+    """call(out, out_root, counts, cap, n_out) -> rc, retried with room on
+    NICE_ERR_CAPACITY."""
+    counts = (ctypes.c_uint64 * max(n_roots, 1))()
+    (out, idx), n = _with_room(lambda o, r, *a: call(o, r, counts, *a), max(cap, 4096),
+                               lambda c: ((ctypes.c_uint64 * (4 * c))(), (ctypes.c_uint32 * c)()))
+    return RangeBounds(out, n, idx), list(counts[:n_roots])
+
+
+def msd_ranges_cpu(roots, base: int, floor_size: int = 250, filter: str = "reference", threads: int = 1,
+                   cap: int = 0):
+    """GpuContext.msd_ranges on the host cores (nice_cpu_msd_ranges): the host
+    recursion root by root, no device."""
+    rb, n_roots = _pack_ranges(roots)
+    return _msd_ranges_call(
+        lambda *a: lib().nice_cpu_msd_ranges(base, rb, n_roots, floor_size, _FILTERS[filter], threads, *a),
+        n_roots, cap)
+
+
+def msd_ranges_plan(roots, base: int, floor_size: int = 250, n_devices: int = 1):
+    """nice_debug_msd_ranges_plan: per root (index, group, device, batch);
+    group 1 is one workgroup per root, 0 the level BFS.  No device."""
+    rb, n_roots = _pack_ranges(roots)
+    n = ctypes.c_size_t()
+    buf = (ctypes.c_uint64 * (4 * max(n_roots, 1)))()
+    check(lib().nice_debug_msd_ranges_plan(base, rb, n_roots, floor_size, n_devices, buf, n_roots, n))
+    w = list(buf[:4 * n.value])
+    return [tuple(w[i:i + 4]) for i in range(0, len(w), 4)]
+
+
+def chunk_roots(start: int, end: int, chunk_size: int = 0) -> RangeBounds:
+    """The roots of a field's chunk grid, as a niceonly field's device MSD takes
+    them: chunks of chunk_size anchored at `start`, the last one ragged;
+    chunk_size 0 is the reference client's rule (client/src/main.rs:158-168),
+    which the field path uses by default.  msd_ranges of these roots is the
+    range list that field's niceonly run tests."""
+    if not 0 <= start < end or end >> 128:
+        raise ValueError("the field must be non-empty and fit in u128")
+    if chunk_size == 0:
+        mult = -(-(end - start) // (1_000_000 * 100_000))
+        chunk_size = 1_000_000 * max(1, min(mult, 1000))
+    n = -(-(end - start) // chunk_size)
+    if max(end, start) <= MASK64:
+        flat = array.array("Q", bytes(32 * n))
+        flat[0::4] = array.array("Q", range(start, end, chunk_size))
+        flat[2::4] = array.array("Q", list(range(start + chunk_size, end, chunk_size)) + [end])
+    else:
+        flat = array.array("Q", [x for a in range(start, end, chunk_size) for b in (min(a + chunk_size, end),)
+                                 for x in (a & MASK64, a >> 64, b & MASK64, b >> 64)])
+    return RangeBounds((ctypes.c_uint64 * len(flat)).from_buffer_copy(flat), n)
 
 
 def _ranges_niceonly_results(cand, lst, base: int) -> List[FieldResults]:

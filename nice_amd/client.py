@@ -84,6 +84,9 @@ def parse_args(argv=None):
                         "and numbers found in the same stratified windows, under the reference and the sound "
                         "filter (nice_amd/survey.py survey_niceonly_base); with --gpu on the GPU; --msd-floor "
                         "as a number (0 = 250)")
+    p.add_argument("--survey-msd", choices=("host", "device"), default="host",
+                   help="--survey-niceonly: where the windows' MSD filter runs -- the host recursion per "
+                        "window, or (with --gpu) one device range-list call per filter (GpuContext.msd_ranges)")
     p.add_argument("--survey-classes", type=int, default=None, metavar="M",
                    help="survey --base by residue class: the table [n mod M][num_uniques] of the same "
                         "stratified windows, from the per-number map (nice_amd/survey.py class_distribution); "
@@ -236,10 +239,13 @@ def run_survey_niceonly(args, ctx) -> int:
     if args.msd_floor == "adaptive":
         log.error("--survey-niceonly needs a numeric --msd-floor")
         return 2
+    if args.survey_msd == "device" and ctx is None:
+        log.error("--survey-msd device needs --gpu")
+        return 2
     floor = args.msd_floor or 250
     t0 = time.perf_counter()
     r = survey_niceonly_base(ctx, args.base, args.windows, args.window_size, args.seed, floor,
-                             threads=max(1, args.threads))
+                             threads=max(1, args.threads), msd_where=args.survey_msd)
     elapsed = time.perf_counter() - t0
     log.info("✓ Surveyed %.2e numbers of base %d for niceonly in %.2fs", r.sampled, args.base, elapsed)
     out = {"base": r.base, "windows": len(r.windows), "window_size": args.window_size, "seed": args.seed,

@@ -271,6 +271,8 @@ void nice_ctx_destroy(nice_ctx *ctx) {
         ranges_nice_dev_free(ctx->devs[i], ctx->ranges_nice.dev[i]);
     for (size_t i = 0; i < ctx->map.dev.size() && i < ctx->devs.size(); i++)
         map_dev_free(ctx->devs[i], ctx->map.dev[i]);
+    for (size_t i = 0; i < ctx->msd_ranges.dev.size() && i < ctx->devs.size(); i++)
+        msd_ranges_dev_free(ctx->devs[i], ctx->msd_ranges.dev[i]);
     for (auto &d : ctx->devs) device_free(d);
     delete ctx;
 }

@@ -22,6 +22,7 @@
 //   abi_ranges.cpp     batched detailed ranges
 //   abi_ranges_niceonly.cpp  batched niceonly ranges
 //   abi_map.cpp        the per-number unique-count map
+//   abi_msd_ranges.cpp the device MSD recursion's range list
 //   abi_hooks.cpp      debug and check hooks
 //   host_parallel.cpp  host thread count and the adaptive MSD floor (no HIP)
 #pragma once
@@ -297,10 +298,38 @@ struct MapState {
     nice_map_stats stats{};
 };
 
+struct MsdRangesDev {
+    SideStream side;              // ev0 / ev1: around a batch's recursion
+    hipEvent_t so0 = nullptr, so1 = nullptr;  // ... and around its sort
+    StagePair roots;              // MsdRangeRoot records of a batch
+    StagePair lists;              // its groups' root indices (u32)
+    MsdNode *q[2] = {nullptr, nullptr};  // level queues
+    size_t q_cap = 0;
+    uint64_t *rec = nullptr;      // 4 x rec_cap u64: keys, sizes, and the sort's output of both
+    size_t rec_cap = 0;
+    ChunkNode *scratch = nullptr; // the workgroup-per-root form's queues
+    size_t scratch_nodes = 0;
+    void *sort_tmp = nullptr;
+    size_t sort_bytes = 0;
+    uint32_t *d_ctl = nullptr;    // level sizes, record count, overflow flag (layout.h's indices)
+    uint32_t *h_ctl = nullptr;    // pinned: the last two after a batch
+    uint64_t *h_rec = nullptr;    // pinned, 2 x h_rec_cap u64: a batch's ordered keys, then its sizes
+    size_t h_rec_cap = 0;
+};
+struct MsdRangesState : KeptList {  // key: the filter; Entry: a range's start and its root index
+    std::vector<MsdRangesDev> dev;
+    nice_msd_ranges_stats stats{};
+    uint64_t floor_size = 0;
+    std::vector<uint64_t> sizes;   // parallel to the list
+    std::vector<uint64_t> counts;  // ranges per root
+};
+
 }  // namespace abi
 }  // namespace nice
 
 struct nice_ctx {
+    std::mutex msd_ranges_mu;  // serialises nice_msd_ranges
+    nice::abi::MsdRangesState msd_ranges;
     std::mutex map_mu;  // serialises nice_unique_map
     nice::abi::MapState map;
     std::mutex ranges_mu;  // ... nice_process_ranges_detailed
@@ -567,6 +596,7 @@ int resolve_stats(Device &d);
 void ranges_dev_free(Device &d, RangesDev &r);
 void ranges_nice_dev_free(Device &d, RangesNiceDev &r);
 void map_dev_free(Device &d, MapDev &r);
+void msd_ranges_dev_free(Device &d, MsdRangesDev &r);
 
 }  // namespace abi
 }  // namespace nice

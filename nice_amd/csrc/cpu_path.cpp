@@ -24,6 +24,7 @@
 #include "../../include/nice_hip.h"
 #include "host_math.hpp"
 #include "niceonly_bases.h"
+#include "msd_ranges_plan.hpp"
 #include "niceonly_ranges_plan.hpp"
 
 namespace {
@@ -390,6 +391,48 @@ extern "C" int nice_cpu_process_ranges_niceonly(uint32_t base, const uint64_t *b
         for (u128 n : ans[i].nice) {
             out[q] = nice_number{(uint64_t)n, (uint64_t)(n >> 64), base, 0};
             if (out_range) out_range[q] = (uint32_t)i;
+            q++;
+        }
+    return NICE_OK;
+}
+
+// nice_msd_ranges on the host cores: the host recursion root by root.
+extern "C" int nice_cpu_msd_ranges(uint32_t base, const uint64_t *roots, size_t n_roots, uint64_t floor_size,
+                                   uint32_t filter, int32_t threads, uint64_t *out, uint32_t *out_root,
+                                   uint64_t *counts, size_t cap, size_t *n_out) {
+    if (!roots || !n_out || (cap && !out)) return cpu_fail(NICE_ERR_INVALID, "null argument");
+    if (filter > NICE_FILTER_SOUND)
+        return cpu_fail(NICE_ERR_INVALID, "filter must be NICE_FILTER_REFERENCE or NICE_FILTER_SOUND");
+    {
+        const std::string why = nice::msd_ranges_check(base, roots, n_roots, floor_size);
+        if (!why.empty()) return cpu_fail(NICE_ERR_INVALID, why.c_str());
+    }
+    const std::unique_ptr<nice::MsdRunner> msd = nice::make_msd(base);
+    std::vector<std::vector<std::pair<u128, u128>>> ans(n_roots);
+    std::atomic<size_t> next{0};
+    auto run = [&] {
+        for (size_t i; (i = next.fetch_add(1)) < n_roots;)
+            msd->ranges(nice::range_at(roots, i, 0), nice::range_at(roots, i, 1), floor_size, ans[i],
+                        filter == NICE_FILTER_SOUND);
+    };
+    const int nt = nthreads(threads, n_roots);
+    std::vector<std::thread> ws;
+    for (int i = 0; i + 1 < nt; i++) ws.emplace_back(run);
+    run();  // the caller's thread
+    for (auto &w : ws) w.join();
+    size_t total = 0;
+    for (size_t i = 0; i < n_roots; i++) {
+        if (counts) counts[i] = ans[i].size();
+        total += ans[i].size();
+    }
+    *n_out = total;
+    if (total > cap) return cpu_fail(NICE_ERR_CAPACITY, "output capacity too small (n_out = required)");
+    size_t q = 0;
+    for (size_t i = 0; i < n_roots; i++)
+        for (const auto &r : ans[i]) {
+            out[4 * q] = (uint64_t)r.first, out[4 * q + 1] = (uint64_t)(r.first >> 64);
+            out[4 * q + 2] = (uint64_t)r.second, out[4 * q + 3] = (uint64_t)(r.second >> 64);
+            if (out_root) out_root[q] = (uint32_t)i;
             q++;
         }
     return NICE_OK;

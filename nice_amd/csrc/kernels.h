@@ -261,6 +261,39 @@ hipError_t launch_msd_device(const MsdLaunch &p, int num_cus, hipStream_t s, Chu
 hipError_t launch_msd_wave(const MsdLaunch &p, const NiceonlyLaunch &c, uint32_t level0, void *scratch,
                            uint32_t grid, int num_cus, hipStream_t s, const SoundLaunch *snd = nullptr);
 
+// The recursion's range list (nice_msd_ranges; msd_ranges.hpp, the run-time-base
+// instances and the sort in msd_ranges.hip, the fast bases' in the objects of
+// msd_ranges_part.hip): the roots of a batch, and what one group of them --
+// one kernel form, one base placement -- runs with.
+struct MsdRangeRoot {
+    uint64_t start_lo, start_hi, size;
+    uint32_t in_range;  // the root lies inside the base's valid range (MsdLaunch::in_range of its nodes)
+    uint32_t pad;
+};
+struct MsdRangesLaunch {
+    const MsdRangeRoot *roots;  // the batch's roots
+    const uint32_t *list;       // the group's roots, as indices into `roots`
+    uint32_t n;                 // ... and how many
+    uint64_t floor_size;
+    MsdNode *q[2];              // form 0: ping-pong level queues; a node's off is root << 40 | offset
+    uint32_t q_cap;
+    uint32_t *ctl;              // kMsdLevels level sizes (per group), kMsdLeafCount and kMsdOverflow (per batch)
+    uint64_t *keys, *sizes;     // the leaf records: root << 40 | offset, and the size
+    uint32_t leaf_cap;
+};
+// Enqueue one group.  fast: the compile-time kernels of `base` (a niceonly fast
+// base; a missing kernel is an error), else the run-time-base ones.  scratch:
+// form 1, one launch of `grid` workgroups (grid x 2 x cap ChunkNodes); null:
+// form 0, init + the levels that a root of max_size numbers can reach.
+hipError_t launch_msd_ranges(const MsdRangesLaunch &p, uint32_t base, bool fast, bool sound, uint64_t max_size,
+                             int num_cus, hipStream_t s, ChunkNode *scratch, uint32_t cap, uint32_t grid,
+                             uint32_t *launches);
+// The records ordered by key (60 bits) on the device: temporary bytes for n
+// records, and the sort (async on s) into keys_out / sizes_out.
+hipError_t msd_ranges_sort_bytes(size_t n, size_t *bytes);
+hipError_t msd_ranges_sort(void *temp, size_t temp_bytes, uint64_t *keys, uint64_t *keys_out, uint64_t *sizes,
+                           uint64_t *sizes_out, size_t n, hipStream_t s);
+
 // Diagnostics used by the parity tests: per-n unique counts / nice flags
 // computed by the same device functions the production kernels use.
 hipError_t launch_unique_counts(const uint64_t *n_pairs, uint32_t count, uint32_t base,

@@ -182,9 +182,27 @@ def _msd_ranges(window, base, floor, filt):
             for r in api.get_valid_ranges(api.FieldSize(s, e), base, floor, filt)]
 
 
+def _device_filter_survey(ctx, w, base, floor, filt) -> NiceonlyFilterSurvey:
+    """One filter's column with the MSD recursion on the device: the windows
+    are the roots of ctx.msd_ranges, its bounds the ranges of niceonly_ranges."""
+    n_ranges = numbers = cand = sq = 0
+    found: List[int] = []
+    for i in range(0, len(w), NICEONLY_BATCH):
+        bounds, _ = ctx.msd_ranges(w[i:i + NICEONLY_BATCH], base, floor, filt)
+        n_ranges += len(bounds)
+        numbers += bounds.numbers()
+        for j in range(0, len(bounds), NICEONLY_BATCH):
+            part = bounds if len(bounds) <= NICEONLY_BATCH else bounds.part(j, j + NICEONLY_BATCH)
+            c, q, lst = ctx.niceonly_ranges(part, base)
+            cand += sum(c)
+            sq += sum(q)
+            found += [n for n, _ in lst]
+    return NiceonlyFilterSurvey(filt, n_ranges, numbers, cand, sq, found)
+
+
 def survey_niceonly_base(ctx: Optional[api.GpuContext], base: int, windows: int = 4096,
                          window_size: int = 10 ** 6, seed: int = 0, msd_floor: int = 250,
-                         threads: int = 1) -> NiceonlySurveyResult:
+                         threads: int = 1, msd_where: str = "host") -> NiceonlySurveyResult:
     """What a niceonly search of `base` would cost, from the stratified windows
     of survey_windows.  Per window the MSD filter (nice_msd_valid_ranges_ex,
     floor msd_floor) runs on `threads` host threads, once under the reference
@@ -195,6 +213,11 @@ def survey_niceonly_base(ctx: Optional[api.GpuContext], base: int, windows: int 
     through scaled() each of these scaled to the whole base range.  No time
     estimate: nothing here has measured one.
 
+    msd_where="device" (needs ctx): the MSD filter of all windows runs on the
+    GPU instead, one ctx.msd_ranges call per filter (per 2^20 windows), and its
+    range list goes to ctx.niceonly_ranges as it is.  Both placements return
+    equal results.
+
     The sound column counts the candidates of the ranges the sound MSD filter
     leaves, i.e. BEFORE the field path's per-candidate prefix test, which
     rejects some of them ahead of the square test (that test needs the MSD
@@ -203,6 +226,10 @@ def survey_niceonly_base(ctx: Optional[api.GpuContext], base: int, windows: int 
     ranges inside the valid range -- every window is); elsewhere it reads 0
     there, while the CPU twin counts it for every base.
     Deterministic in `seed`."""
+    if msd_where not in ("host", "device"):
+        raise ValueError("msd_where must be 'host' or 'device'")
+    if msd_where == "device" and ctx is None:
+        raise ValueError("msd_where='device' needs a GpuContext")
     w = survey_windows(base, windows, window_size, seed)
     r = api.get_base_range_u128(base)
     # windows no larger than the floor: the MSD recursion emits each untested
@@ -216,6 +243,9 @@ def survey_niceonly_base(ctx: Optional[api.GpuContext], base: int, windows: int 
                 continue
             if small:
                 ranges = list(w)
+            elif msd_where == "device":
+                per_filter[filt] = _device_filter_survey(ctx, w, base, msd_floor, filt)
+                continue
             else:
                 ranges = [x for rs in pool.map(lambda win: _msd_ranges(win, base, msd_floor, filt), w)
                           for x in rs]
