@@ -80,7 +80,7 @@ def main():
     ctx = N.GpuContext(0)
     try:
         kw = dict(windows=48, window_size=2500, seed=11)
-        out = {"device_mode": {str(b): device_mode(ctx, b) for b in (40, 80)},
+        out = {"device_mode": {str(b): device_mode(ctx, b) for b in (40, 60, 80)},
                "device_errors": device_errors(ctx),
                "class_table": survey.class_distribution(ctx, 40, 39, **kw),
                "survey_distribution": survey.survey_base(ctx, 40, **kw).distribution}

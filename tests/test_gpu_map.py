@@ -10,6 +10,7 @@ import ctypes
 import functools
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -20,9 +21,29 @@ import nice_amd as N
 from nice_amd import _lib, api, survey
 from oracle import oracle as O
 
+import fd_carry_points as F
+import near_miss_windows as W
+from test_map import plan as map_plan
+
 pytestmark = pytest.mark.gpu
 MASK = (1 << 64) - 1
-LONG = 100_003  # three workgroups of b40's 512 x 81 tile, a partial last one, a tail workgroup
+# Up to b58 (512 lanes, target chunk 81 or 161): full workgroups, a partial last one and a tail
+# workgroup.  From b59 on (1024 or 512 lanes, target chunk 241) one partial workgroup of 1010 / 507
+# lanes walking 99 / 197 numbers each -- several ring flushes per lane -- and a tail; full_size()
+# is the window with a full workgroup at every base.
+LONG = 100_003
+FD_BASES = W.fd_bases()
+
+
+def full_size(base):
+    """Workgroup x target chunk + 1 numbers: two main workgroups, the first
+    with all its lanes, and a tail."""
+    rs, _ = O.base_range(base)
+    wg = max(r[3] for r in map_plan(base, rs, rs + 10 ** 6))
+    size = wg * ((80 if base <= 45 else 160 if base <= 58 else 240) + 1) + 1
+    recs = map_plan(base, rs, rs + size)
+    assert wg in (512, 1024) and [r[3] == wg for r in recs] == [True, False, False] and recs[-1][4] == 1
+    return size
 
 
 @pytest.fixture(scope="module")
@@ -34,8 +55,15 @@ def ctx():
 
 @functools.lru_cache(maxsize=None)
 def oracle_map(a, b, base):
-    """The oracle's count of every n in [a, b), computed once per range."""
-    return np.frombuffer(bytes(O.num_unique_digits(n, base) for n in range(a, b)), dtype=np.uint8)
+    """The oracle's count of every n in [a, b), computed once per range: one
+    process_range_detailed call that lists every number (cutoff 0), and for
+    short ranges and at both ends num_unique_digits number by number."""
+    r = O.process_range_detailed(a, b, base, cap=b - a, cutoff=0)
+    assert [n for n, _ in r.nice_numbers] == list(range(a, b))
+    m = np.array([u for _, u in r.nice_numbers], dtype=np.uint8)
+    for n in list(range(a, b)) if b - a <= 1000 else [*range(a, a + 100), *range(b - 100, b)]:
+        assert m[n - a] == O.num_unique_digits(n, base)
+    return m
 
 
 def cuts_of(base):
@@ -53,16 +81,36 @@ def same(got, want):
 
 
 # --- 1. oracle parity ---------------------------------------------------------------------
-@pytest.mark.parametrize("base", [40, 45, 50, 64, 68, 80])
+def layouts_in_combos_h(base):
+    """The base's limb layouts in fd2_combos.h: one fd2_map_kernel (and one
+    fd2_batch_kernel) instantiation each."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "nice_amd", "csrc", "fd2_combos.h")) as f:
+        text = f.read()
+    combos = re.findall(r"X\((\d+), \d+, \d+, \d+\)", text[text.index("#define FD2_COMBOS"):])
+    assert len(combos) == 37
+    return combos.count(str(base))
+
+
+def test_the_old_bases_are_fd_bases():
+    assert set(FD_BASES) >= {40, 45, 50, 64, 68, 80} and len(FD_BASES) == 24
+
+
+@pytest.mark.parametrize("base", FD_BASES)
 def test_fd_map_equals_oracle(ctx, base):
-    """b40 / b45 / b50 (low-digit table), b64 (side carry table, 1024 threads),
-    b68 / b80 (three mask words; n above 64 bits, so init_at from the
-    descriptor's digits).  From the range start: a lone tail workgroup (1, 63),
-    one partial workgroup (4 097: chunk 9, so lane runs start at every residue
-    mod 16) and several workgroups with a partial last wave and a tail
-    (100 003); across the first limb-layout cut; across the range end, where the
-    FD kernel hands over to the generic one inside one call."""
-    rs, re = O.base_range(base)
+    """Every base with an FD kernel, every limb layout of it (each is an
+    fd2_map_kernel instantiation of its own, and walk_map branches on the
+    per-base switches of the kernel configuration: low-digit table or LSDX,
+    TIGHT entry, one to three mask words, limbs decoded by VALU, 512 or 1024
+    threads, n above 64 bits so that init_at takes the descriptor's digits).
+    From the range start: a lone tail workgroup (1, 63), one partial workgroup
+    (4 097: chunk 9, so lane runs start at every residue mod 16) and several
+    workgroups with a partial last wave and a tail (100 003).  For every layout:
+    100 003 numbers and a full workgroup, a partial one and a tail (full_size)
+    from its first n, and 4 097 numbers ending at its last.  Across
+    every limb-layout cut; across the range end and start, where the FD kernel
+    and the generic one share one call."""
+    rs, r1 = O.base_range(base)
     want = oracle_map(rs, rs + LONG, base)
     for size in (1, 63, 4097, LONG):
         same(ctx.unique_map(rs, rs + size, base), want[:size])
@@ -70,13 +118,23 @@ def test_fd_map_equals_oracle(ctx, base):
         assert (st.fd_numbers, st.generic_numbers, st.generic_segments) == (size, 0, 0) and st.fd_segments == 1
         assert st.launches == 1
     cuts = cuts_of(base)
-    # (b64 and b68 have one limb layout and so no cut: the same window in mid-range)
-    assert bool(cuts) == (base not in (64, 68))
-    c = cuts[0] if cuts else rs + (re - rs) // 2
-    same(ctx.unique_map(c - 300, c + 300, base), oracle_map(c - 300, c + 300, base))
-    st = ctx.map_stats()
-    assert st.fd_segments == (2 if cuts else 1) and st.fd_numbers == 600 and st.launches == st.fd_segments
-    same(ctx.unique_map(re - 150, re + 150, base), oracle_map(re - 150, re + 150, base))
+    # one cut between neighbouring layouts: by the limb counts' own arithmetic and by the header
+    assert cuts == F.layout_cuts(base) and len(cuts) + 1 == layouts_in_combos_h(base)
+    assert bool(cuts) == (layouts_in_combos_h(base) > 1)
+    if base in (64, 68):
+        assert not cuts
+    edges = [rs] + cuts + [r1]
+    for a, e in zip(edges, edges[1:]):
+        for x, y in ((a, a + LONG), (a, a + full_size(base)), (e - 4097, e)):
+            same(ctx.unique_map(x, y, base), oracle_map(x, y, base))
+            st = ctx.map_stats()
+            assert (st.fd_segments, st.fd_numbers, st.generic_numbers, st.launches) == (1, y - x, 0, 1), (x, y)
+    # (a base with one limb layout has no cut: the same window in mid-range)
+    for c in cuts or [rs + (r1 - rs) // 2]:
+        same(ctx.unique_map(c - 300, c + 300, base), oracle_map(c - 300, c + 300, base))
+        st = ctx.map_stats()
+        assert st.fd_segments == (2 if cuts else 1) and st.fd_numbers == 600 and st.launches == st.fd_segments
+    same(ctx.unique_map(r1 - 150, r1 + 150, base), oracle_map(r1 - 150, r1 + 150, base))
     st = ctx.map_stats()
     assert (st.fd_numbers, st.generic_numbers, st.fd_segments, st.generic_segments) == (150, 150, 1, 1)
     same(ctx.unique_map(rs - 150, rs + 150, base), oracle_map(rs - 150, rs + 150, base))
@@ -119,12 +177,14 @@ def torch_child():
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
-@pytest.mark.parametrize("base", [40, 80])
+@pytest.mark.parametrize("base", [40, 60, 80])
 def test_device_mode_writes_in_place_at_any_alignment(ctx, torch_child, base):
     """Views at 0, 1, 3 and 15 mod 16 of one owned allocation with at least 64
     guard bytes on either side (100 003 numbers; 63: a lone tail workgroup; a
     tensor longer than the range): the interior equals the host-mode map and no
-    guard byte changes (an overrun shows as a failed comparison, not a fault)."""
+    guard byte changes (an overrun shows as a failed comparison, not a fault).
+    b40 and b80 run 512 threads; b60 runs 1024, so the ring's dword stride is
+    4 x 1024, and its low-digit table has the side carry table."""
     d = torch_child["device_mode"][str(base)]
     assert d["aligned"]
     assert [(r["off"], r["n"]) for r in d["runs"]] == [(64, LONG), (65, LONG), (67, LONG), (79, LONG), (64, 63),

@@ -61,15 +61,26 @@ def check_rows(ctx, ranges, base):
 
 
 # --- 1. edge sizes against the oracle ----------------------------------------------
-@pytest.mark.parametrize("base", [40, 52, 62, 80])
+FD_BASES = [b for b in range(2, 129) if _lib.lib().nice_fd_kernel_base(b) == 1]
+
+
+def test_the_old_bases_are_fd_bases():
+    assert {40, 52, 62, 80} <= set(FD_BASES) and len(FD_BASES) == 24
+
+
+@pytest.mark.parametrize("base", FD_BASES)
 def test_edge_sizes_match_oracle(ctx, base):
-    """One base per FD layout class (one / two / three mask words; low-digit
-    table, LSDX, no low-digit table): every size at which the plan changes
-    shape, at the range's first and last n, across every cut and at seeded
-    interior points, in ONE call."""
+    """Every base with an FD kernel (one / two / three mask words; low-digit
+    table, LSDX, no low-digit table; TIGHT entry; limbs decoded by VALU; 512 and
+    1024 threads): every size at which the plan changes shape, at the range's
+    first and last n, a full workgroup and one number from the first n of every
+    limb layout and up to its last -- so every fd2_batch_kernel instantiation
+    of the base runs -- across every cut and at seeded interior points, in ONE
+    call of one launch per layout."""
     s, e = O.base_range(base)
     cuts = cuts_of(base)
     wg, chunk = shape_of(base)
+    assert wg in (512, 1024)
     sizes = (1, 2, 63, 64, 65, chunk - 1, chunk, chunk + 1, wg - 1, wg, wg + 1, wg * chunk, wg * chunk + 1)
     rng = random.Random(100 + base)
     ranges = []
@@ -83,9 +94,11 @@ def test_edge_sizes_match_oracle(ctx, base):
             at_s, at_e = at_s + size, at_e - size
     ranges += [(s, s + 1), (e - 1, e), (s, s + wg * chunk + 1), (e - wg * chunk - 1, e)]
     ranges += [(c - 1000, c + 1000) for c in cuts]
+    # the same two at the inner ends of every limb layout (the cut is the next layout's first n)
+    ranges += [r for c in cuts for r in ((c - wg * chunk - 1, c), (c, c + wg * chunk + 1))]
     check_rows(ctx, ranges, base)
     st = ctx.ranges_stats()
-    assert 1 <= st.launches <= len(cuts) + 1 and st.fallback_ranges == 0
+    assert st.launches == len(cuts) + 1 and st.fallback_ranges == 0
     assert st.numbers == sum(b - a for a, b in ranges)
 
 

@@ -94,15 +94,23 @@ def check_plan(base, s, e, wg_max):
     return recs
 
 
-@pytest.mark.parametrize("base", [40, 50, 64, 80])
+FD_BASES = [b for b in range(2, 129) if _lib.lib().nice_fd_kernel_base(b) == 1]
+
+
+@pytest.mark.parametrize("base", FD_BASES)
 def test_plan_tiles_the_range(base):
-    """One base per shape of the FD kernel: b40 and b50 (low-digit table, 512
-    threads), b64 (side carry table, 1024 threads), b80 (three mask words, n
-    above 64 bits: the descriptors' digits feed init_at)."""
+    """Every base with an FD kernel; among them one per shape: b40 and b50
+    (low-digit table, 512 threads), b64 (side carry table, 1024 threads), b80
+    (three mask words, n above 64 bits: the descriptors' digits feed init_at).
+    The workgroup size is the plan's own: the lanes of a full workgroup."""
+    assert {40, 50, 64, 80} <= set(FD_BASES) and len(FD_BASES) == 24
     rs, re = O.base_range(base)
     cuts = cuts_of(base)
-    assert (cuts or base == 64) and _lib.lib().nice_fd_kernel_base(base) == 1  # b64: one limb layout, no cut
-    wg = 1024 if base == 64 else 512
+    assert len(cuts) <= 2 and (cuts or base not in (40, 50, 80))  # (b64, for one, has one limb layout and no cut)
+    wg = max(r[3] for r in plan(base, rs, rs + 10 ** 6))
+    assert wg in (512, 1024)
+    if base in (40, 50, 64, 80):
+        assert wg == (1024 if base == 64 else 512)
     sizes = (1, 63, 64 * 80 + 1, 100_003)
     for size in sizes:
         recs = check_plan(base, rs, rs + size, wg)
