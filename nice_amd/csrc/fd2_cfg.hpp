@@ -434,8 +434,32 @@ struct Cfg {
     // their lookups pile onto few bank quads
     static constexpr bool VDL = ((VD & 256) != 0 || NOTAB) && !LSD;
     static constexpr u32 MAGIC_D = (u32)(((1ull << 32) + ES * BASE - 1) / (ES * BASE));
+    // VD & 262144: the step's carry adds and limb reductions on the f32 FMA
+    // pipe (fma_bits, fd2_kernel.hpp): exact while every operand and result is
+    // an integer in [0, 2^24] and no FMA operand has wrapped below zero.  In
+    // the step's order (c the carry, 0..4, travelling unscaled):
+    //   t1 = ES c + C        FMA; C a state limb, < DC + 4 ES (the top stepped
+    //                        limb before rare()), never negative
+    //   t  = 3 S + t1 + N3   integer (v_mad_u32_u24, the 3 an inline constant;
+    //                        N3's offset limbs wrap on purpose); the true sum
+    //                        is in [0, TMAX]: a C-limb sum is < 5B + 4
+    //   C  = t - c DC        FMA; c = t / DC, so the result is in [0, DC)
+    //   t  = ES c + (S + D1) FMA; S biased, so t in [ES BT, 2^(SH+1))
+    //   S  = t - c DC        FMA; c = [t >= 2^SH], and 2^SH >= DC = ES B
+    // (3.0 as a third VGPR constant, or or_valu's -BASE as a fourth, spilled.)
+    // The off state is the integer form (v_lshl_add_u32 / v_mad_i32_i24).
+    static constexpr bool FMA = (VD_ & 262144) != 0;
+    static constexpr unsigned long long FMA_LIM = 1ull << 24;
+    static constexpr unsigned long long FMA_T1 = 4ull * ES + DC + 4ull * ES;  // max ES c + C
+    static constexpr unsigned long long FMA_TS = 2ull << SH;                  // S-limb sum bound
+    static_assert(!FMA || (TMAX <= FMA_LIM && FMA_T1 <= FMA_LIM && 5ull * DC <= FMA_LIM && FMA_TS <= FMA_LIM),
+                  "f32-pipe limb arithmetic: operands and results within 2^24");
+    // the reductions' results are non-negative: C's carry is t / DC (exact:
+    // the carry-magic assert below), S's is one DC taken off t >= 2^SH >= DC
+    static_assert(!FMA || (TMAX / DC <= 5 && (1ull << SH) >= DC),
+                  "f32-pipe limb arithmetic: no reduction below zero");
     static_assert(VD == 0 || (MW >= 2 && split_exact(BASE, ES, MAGIC_D)), "VALU digit split");
-    static_assert(VDC <= NE + 1 - (MW <= 2 ? 1 : 0) && VDS <= ND + 1 && (VD & ~0x3ffff) == 0 &&
+    static_assert(VDC <= NE + 1 - (MW <= 2 ? 1 : 0) && VDS <= ND + 1 && (VD & ~0x7ffff) == 0 &&
                       ((VD & 1024) == 0 || LSDX),
                   "VALU-decoded limbs");
     // Waves per SIMD: what the LDS allows, capped by what the lane state

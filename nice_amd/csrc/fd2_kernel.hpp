@@ -46,6 +46,16 @@
 //    sibling parts on such a grid too (Cfg::SIBPERS, two 512-thread
 //    workgroups per CU; fd2_plan.hpp plan_sib_pers).
 //
+//  * Cfg::FMA (b40's sibling kernels): the step's shift-adds and limb
+//    reductions (C + ES c, t - c DC; 3 S + t keeps its integer multiply-add,
+//    whose 3 is an inline constant: a third VGPR constant spilled) run on the f32 FMA
+//    pipe on the limbs' bit patterns (fma_bits: a small integer's pattern is
+//    a subnormal, and the FMA of such patterns is exact), the carries of both
+//    chains travelling unscaled from limb to limb.  On gfx950 a v_fma_f32 of
+//    VGPRs issues in ~2.6 cycles, the integer forms in ~4.4 (and anything
+//    with an SGPR operand in ~4.3, hence the constants in VGPRs).  The
+//    kernels must keep f32 subnormals (the compiler's default mode).
+//
 // The kernel is issue-bound on VALU and LDS together: b40 per n is 13 random
 // 8-byte LDS lookups (≈5 LDS cycles each per wave) and ≈78 VALU instructions
 // per wave-step; see DESIGN.md §3.1 for the cycle model and the measured
@@ -75,6 +85,28 @@ template <int K>
 __device__ __forceinline__ u32 mad_i24s(u32 a, u32 c) {
     u32 r;
     asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(K), "v"(c));
+    return r;
+}
+
+// a * K + c on the f32 FMA pipe, for integers: returns the bits of the integer
+// a K + c (Cfg::FMA).  A u32 bit pattern x <= 2^24 read as an IEEE f32 is
+// exactly x 2^-149 -- a subnormal below 2^23, and the first normal binade
+// continues the same line -- so with a true float K the FMA of two such
+// patterns is (a K + c) 2^-149: exact in every rounding mode, nothing being
+// rounded, while a, c and a K + c are integers in [0, 2^24] (Cfg's
+// static_asserts; the kernels keep f32 subnormals, the compiler's default,
+// see the Makefile).  An integer that wrapped below zero is a NaN pattern
+// here: such terms (N3's offset limbs, -3 ES BT) are added after the FMAs,
+// as integers.  No conversion anywhere: the same register is still the limb's
+// LDS byte offset and a multiply-high's operand.  K sits in a VGPR: on gfx950
+// a v_fma_f32 of VGPRs (or an inline constant) issues in ~2.6 cycles against
+// ~4.4 for the integer multiply-adds and shift-adds it replaces, but ANY
+// instruction with an SGPR operand in ~4.3 (profiles/fma/isa_issue_rates.log).
+template <int K>
+__device__ __forceinline__ u32 fma_bits(u32 a, u32 c) {
+    u32 r;
+    const float k = (float)K;
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(k), "v"(c));
     return r;
 }
 
@@ -450,6 +482,45 @@ __device__ __forceinline__ void rare(State<P> &st, const unsigned char *smem, u3
     if (cS | cC) recompute_hi<P>(st, smem);
 }
 
+// The two arithmetics of a limb chain (Cfg::FMA), in three places each: the
+// carry coming in, a bare carry being scaled, and the limb's reduction, which
+// returns the carry in the form the chain passes on -- the integer form c * ES
+// (S: the bit itself, 0 or ES), the f32 form c unscaled (ES B = DC reduces
+// both chains).  Everything between them is the same code for both.
+template <class P>
+__device__ __forceinline__ u32 carry_in(u32 c, u32 x) {
+    if constexpr (P::FMA) return fma_bits<P::ES>(c, x);
+    else return x + c;
+}
+template <class P>
+__device__ __forceinline__ u32 scale_in(u32 c, u32 x) {  // x + ES c, c bare
+    if constexpr (P::FMA) return fma_bits<P::ES>(c, x);
+    else return mad_u24<P::ES>(c, x);
+}
+template <class P>
+__device__ __forceinline__ u32 c_reduce(u32 &limb, u32 t) {
+    const u32 c = P::C1 ? __umulhi(t, P::MAGIC) : __umulhi(t / P::ES, P::MAGICB);
+    if constexpr (P::FMA) {
+        limb = fma_bits<-(int)P::DC>(c, t);
+        return c;
+    } else {
+        limb = t - c * P::DC;
+        return c * P::ES;
+    }
+}
+template <class P>
+__device__ __forceinline__ u32 s_reduce(u32 &limb, u32 t) {
+    if constexpr (P::FMA) {
+        const u32 c = t >> P::SH;  // t < 2^(SH+1): the bit alone
+        limb = fma_bits<-(int)P::DC>(c, t);
+        return c;
+    } else {
+        const u32 c = (t >> P::T) & P::ES;
+        limb = t - c * P::B;
+        return c;
+    }
+}
+
 // One FD step n -> n+1.  w1 = word 1 of the low-digit entry of n (LSD bases):
 // limb 0 of every quantity lives in the table, so the chains start at limb 1
 // with the table's carries.  The carry leaves each limb as c8 = ES * carry,
@@ -462,6 +533,7 @@ __device__ __forceinline__ void step(State<P> &st, const unsigned char *smem, u3
     constexpr int L0 = P::LO;  // LSD bases: limb 0 lives in the low-digit table
     constexpr int CT = P::CL - 1, ST = P::SL - 1;  // top stepped limbs
     static_assert(CT >= P::NS && CT >= P::NN && ST >= P::ND, "top limbs take carries only");
+    static_assert(CT > L0 && ST > L0, "a stepped limb below the top one: its carry is in the chain's form");
     // C += 3S + N3 (old S), limbs L0 .. CL-1.  Unbiased scaled limbs; a limb
     // sum is < 5B, its carry (0..4) is a multiply-high.
     u32 cC = 0;
@@ -469,8 +541,9 @@ __device__ __forceinline__ void step(State<P> &st, const unsigned char *smem, u3
 #pragma unroll
     for (int i = L0; i < CT; i++) {
         u32 t;
-        if (P::TIGHT && i == L0) t = mad_u24<ES>(cC, st.C[i]);  // scale the bare carry
-        else t = st.C[i] + cC;
+        if (P::TIGHT && i == L0) t = scale_in<P>(cC, st.C[i]);  // scale the bare carry
+        else if (i == L0) t = st.C[i] + cC;  // the table's carry: pre-scaled (or none)
+        else t = carry_in<P>(cC, st.C[i]);
         // Past limb L0 the carry is c * ES from a multiply-high: keep C + c*ES
         // one v_lshl_add_u32 and add N3 with a plain v_add_u32 (LLVM would
         // otherwise emit v_lshlrev_b32 + v_add3_u32, ~2 issue cycles more).
@@ -480,23 +553,21 @@ __device__ __forceinline__ void step(State<P> &st, const unsigned char *smem, u3
         // + 3S as one v_mad_u32_u24 (limbs < 2^24)
         if (i < P::SL) t = mad_u24<3>(st.S[i], t);
         else if (i < P::NS) t = mad_u24<3 * ES>(st.S[i], t);
-        const u32 c = P::C1 ? __umulhi(t, P::MAGIC) : __umulhi(t / ES, P::MAGICB);
-        st.C[i] = t - c * P::DC;
-        cC = c * ES;
+        cC = c_reduce<P>(st.C[i], t);
     }
-    st.C[CT] += cC;  // < DC + 4 ES: a carry out is at most 1
+    st.C[CT] = carry_in<P>(cC, st.C[CT]);  // < DC + 4 ES: a carry out is at most 1
     // S += D1, limbs L0 .. SL-1 (biased: carry = bit T of t >> log2 ES).
     u32 cS = 0;
     if constexpr (P::LSD) cS = __builtin_amdgcn_ubfe(w1, P::F0, P::F0W);  // TIGHT: bare carry
 #pragma unroll
     for (int i = L0; i < ST; i++) {
         u32 t;
-        if (P::TIGHT && i == L0) t = mad_u24<ES>(cS, st.S[i] + (i < P::ND ? st.D1[i] : 0u));
-        else t = st.S[i] + (i < P::ND ? st.D1[i] : 0u) + cS;
-        cS = (t >> P::T) & ES;
-        st.S[i] = t - cS * P::B;
+        if (P::TIGHT && i == L0) t = scale_in<P>(cS, st.S[i] + (i < P::ND ? st.D1[i] : 0u));
+        else if (i == L0) t = st.S[i] + (i < P::ND ? st.D1[i] : 0u) + cS;
+        else t = carry_in<P>(cS, st.S[i] + (i < P::ND ? st.D1[i] : 0u));
+        cS = s_reduce<P>(st.S[i], t);
     }
-    st.S[ST] += cS;
+    st.S[ST] = carry_in<P>(cS, st.S[ST]);
     st.r8 += ES;
     if constexpr (P::LSDX) st.rc += 1;
     const bool topS = st.S[ST] >= (1u << P::SH), topC = st.C[CT] >= P::DC;
@@ -785,13 +856,13 @@ __device__ __forceinline__ void walk_chunk(State<P> &st, const unsigned char *sm
 // cycles per wave-step to 10.5 and ~240.
 // ---------------------------------------------------------------------------
 
-// One C limb i > LO of C += 3S + N3 (old S) with the scaled carry-in cC;
-// returns the scaled carry out (step() does the same inline).  The cached S
+// One C limb i > LO of C += 3S + N3 (old S) with the carry-in cC in the
+// chain's form (c_reduce); returns the carry out (step() does the same inline).  The cached S
 // limbs [SL, NS) of a sibling are held as K = 3 ES S (they change only on the
 // rare path), so their term is one add.
 template <class P>
 __device__ __forceinline__ u32 c_limb(State<P> &st, int i, u32 cC) {
-    u32 t = st.C[i] + cC;
+    u32 t = carry_in<P>(cC, st.C[i]);
     if (i < P::NN) asm("" : "+v"(t));
     if (i < P::NN) t += st.N3[i];
     else if (i < P::SL) t -= 3 * P::EBT;
@@ -800,18 +871,13 @@ __device__ __forceinline__ u32 c_limb(State<P> &st, int i, u32 cC) {
     // (The scaled carry straight from one multiply-high, mulhi(t, ES MAGIC) &
     // -ES, prices 18 cycles fewer per step in the issue budget but measured
     // 0.6-2.2 % slower, interleaved A/B: profiles/r05/carry_c8_ab.log.)
-    const u32 c = P::C1 ? __umulhi(t, P::MAGIC) : __umulhi(t / P::ES, P::MAGICB);
-    st.C[i] = t - c * P::DC;
-    return c * P::ES;
+    return c_reduce<P>(st.C[i], t);
 }
 
-// One S limb i > LO of S += D1 (biased) with the scaled carry-in cS.
+// One S limb i > LO of S += D1 (biased) with the carry-in cS in the chain's form.
 template <class P>
 __device__ __forceinline__ u32 s_limb(State<P> &st, int i, u32 cS) {
-    const u32 t = st.S[i] + (i < P::ND ? st.D1[i] : 0u) + cS;
-    const u32 c = (t >> P::T) & P::ES;
-    st.S[i] = t - c * P::B;
-    return c;
+    return s_reduce<P>(st.S[i], carry_in<P>(cS, st.S[i] + (i < P::ND ? st.D1[i] : 0u)));
 }
 
 // A sibling's cold C limb k (C[CL + k]) in LDS.
@@ -955,11 +1021,11 @@ __device__ __forceinline__ void step_sib(State<P> (&st)[P::SIB], const unsigned 
         u32 c = cC;
 #pragma unroll
         for (int i = L + 1; i < CT; i++) c = c_limb<P>(st[j], i, c);
-        st[j].C[CT] += c;
+        st[j].C[CT] = carry_in<P>(c, st[j].C[CT]);
         u32 cs = cS;
 #pragma unroll
         for (int i = L + 1; i < ST; i++) cs = s_limb<P>(st[j], i, cs);
-        st[j].S[ST] += cs;
+        st[j].S[ST] = carry_in<P>(cs, st[j].S[ST]);
         topS[j] = st[j].S[ST] >= (1u << P::SH);
         topC[j] = st[j].C[CT] >= P::DC;
         any |= topS[j] | topC[j];
@@ -968,7 +1034,7 @@ __device__ __forceinline__ void step_sib(State<P> (&st)[P::SIB], const unsigned 
 }
 
 // step_sib in pieces for the pipelined walk: the shared limb L (returns the
-// scaled carries into limb L + 1 of C and S) ...
+// carries into limb L + 1 of C and S, in the chains' form) ...
 template <class P>
 __device__ __forceinline__ void sib_shared_step(State<P> &s0, u32 w1, u32 &cC, u32 &cS, bool &wrap) {
     constexpr u32 ES = P::ES;
@@ -977,20 +1043,17 @@ __device__ __forceinline__ void sib_shared_step(State<P> &s0, u32 w1, u32 &cC, u
                   "sibling lanes: shared D1 / N3 limb and the low-digit entry's wrap flags");
     cC = __builtin_amdgcn_ubfe(w1, P::FC, P::FCW);
     {
-        u32 t = P::TIGHT ? mad_u24<ES>(cC, s0.C[L]) : s0.C[L] + cC;
+        u32 t = P::TIGHT ? scale_in<P>(cC, s0.C[L]) : s0.C[L] + cC;
         if (L < P::NN) t += s0.N3[L];
         else t -= 3 * P::EBT;
         t = mad_u24<3>(s0.S[L], t);
-        const u32 c = P::C1 ? __umulhi(t, P::MAGIC) : __umulhi(t / ES, P::MAGICB);
-        s0.C[L] = t - c * P::DC;
-        cC = c * ES;
+        cC = c_reduce<P>(s0.C[L], t);
     }
     cS = __builtin_amdgcn_ubfe(w1, P::F0, P::F0W);
     {
         const u32 d = L < P::ND ? s0.D1[L] : 0u;
-        const u32 t = P::TIGHT ? mad_u24<ES>(cS, s0.S[L] + d) : s0.S[L] + d + cS;
-        cS = (t >> P::T) & ES;
-        s0.S[L] = t - cS * P::B;
+        const u32 t = P::TIGHT ? scale_in<P>(cS, s0.S[L] + d) : s0.S[L] + d + cS;
+        cS = s_reduce<P>(s0.S[L], t);
     }
     s0.r8 += ES;
     // limb-0 wraps of D1 / N3 (the entry's flags, one in ~B / 5 steps) step
@@ -1009,10 +1072,10 @@ __device__ __forceinline__ bool sib_upper_step(State<P> &st, u32 cC, u32 cS, boo
     constexpr int CT = P::CL - 1, ST = P::SL - 1;
 #pragma unroll
     for (int i = L + 1; i < CT; i++) cC = c_limb<P>(st, i, cC);
-    st.C[CT] += cC;
+    st.C[CT] = carry_in<P>(cC, st.C[CT]);
 #pragma unroll
     for (int i = L + 1; i < ST; i++) cS = s_limb<P>(st, i, cS);
-    st.S[ST] += cS;
+    st.S[ST] = carry_in<P>(cS, st.S[ST]);
     topS = st.S[ST] >= (1u << P::SH);
     topC = st.C[CT] >= P::DC;
     return topS | topC;

@@ -36,10 +36,17 @@ static hipError_t try_combo(const DetailedLaunch &p, int nd, int ne, int ne2, bo
         // VALU decode (profiles/r05/sib_sweep_range.log).  The pipelined one
         // has a persistent-grid twin (Cfg::SibPers), which launch_sib picks
         // for long pipelined segments (plan_sib_pers)
+        // All three with the limb chains' carry adds and reductions on the f32
+        // FMA pipe (Cfg::FMA, VD & 262144): interleaved against the integer
+        // form on 1e9 fields, 1.74-1.76 vs 1.84-1.85 ms at the range start,
+        // 1.75 vs 1.89 at 0.1, 1.85 vs 1.95 at 0.25 (pipelined), 1.91 vs 2.00 at
+        // 0.35 and 1.94 vs 2.02 at 0.5 (profiles/fma/sib_fma_ab.txt).  The other
+        // bases keep the integer form; their A/B: profiles/fma/bases_fma_ab.txt.
         if constexpr (B_ == 40) {
             if (!wg512) {
-                if constexpr (ND_ == 4) return launch_cfg<Cfg<B_, ND_, NE_, NE2_, 0, 512, 4097, 100, 0, 3>>(p, num_cus, s);
-                else return launch_cfg<Cfg<B_, ND_, NE_, NE2_, 0, 512, 0, 1, 0, 3>>(p, num_cus, s);
+                if constexpr (ND_ == 4)
+                    return launch_cfg<Cfg<B_, ND_, NE_, NE2_, 0, 512, 4097 | 262144, 100, 0, 3>>(p, num_cus, s);
+                else return launch_cfg<Cfg<B_, ND_, NE_, NE2_, 0, 512, 262144, 1, 0, 3>>(p, num_cus, s);
             }
         }
         // b42..45 the same, per-sibling lookup groups: 1e9 at the range start

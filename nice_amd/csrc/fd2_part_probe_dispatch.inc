@@ -93,6 +93,10 @@
             case 143: return launch_cfg<Cfg<B_, ND_, NE_, NE2_, 0, 512, 4098, 1, 0, 3>>(p, num_cus, s);
             case 144: return launch_cfg<Cfg<B_, ND_, NE_, NE2_, 0, 512, 4113, 1, 0, 3>>(p, num_cus, s);
             case 121: return launch_cfg<Cfg<B_, ND_, NE_, NE2_, 0, 512, 4097, 1, 0, 2>>(p, num_cus, s);
+            // 142 / 131 with the limb arithmetic on the f32 FMA pipe (Cfg::FMA):
+            // the production kernels, 142 / 131 being their integer forms
+            case 242: return launch_cfg<Cfg<B_, ND_, NE_, NE2_, 0, 512, 4097 | 262144, 100, 0, 3>>(p, num_cus, s);
+            case 231: return launch_cfg<Cfg<B_, ND_, NE_, NE2_, 0, 512, 262144, 1, 0, 3>>(p, num_cus, s);
             default: break;
             }
         }
