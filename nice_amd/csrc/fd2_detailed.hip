@@ -202,9 +202,7 @@ hipError_t launch_batch_part5(const BatchLaunch &, int, int, int, const void *, 
 static_assert(FD2_NPARTS == 6, "launch_batch_part declarations");
 }  // namespace fd2
 
-uint32_t fd2_batch_wg(uint32_t base) {
-    return (fd2::valu_limbs((int)base) & 1024) ? (uint32_t)fd2::big_wg((int)base) : 512u;
-}
+uint32_t fd2_batch_wg(uint32_t base) { return (uint32_t)fd2::small_wg((int)base); }  // BatchCfg::WG
 
 // The base's TCHUNK (Cfg), made odd as rounds_chunk makes its chunks: odd
 // chunks spread a wave's low-digit entries over distinct bank pairs, and are
@@ -235,10 +233,9 @@ void fd2_batch_plan(uint32_t base, u128 a, u128 e, uint32_t row, std::vector<Bat
 
 namespace fd2 {
 // Whether the batch-configuration kernels' (batch, map) init_at reads a
-// descriptor's xs: only where n passes 64 bits and the kernel keeps 32-bit
-// init columns (Cfg::N64, C64).
+// descriptor's xs (Cfg::N64, C64).
 static bool unit_reads_digits(uint32_t base) {
-    return fd2_supported(base) && !fits64(base, digits_of((int)base).dn) && fd2_batch_wg(base) < 1024;
+    return fd2_supported(base) && reads_host_digits((int)base, small_wg((int)base));
 }
 // A descriptor's xs: zeros, or (`read`) the radix-b^2 digits of its first n.
 static void unit_digits(uint32_t base, bool read, u64 lo, u64 hi, u32 *xs) {

@@ -32,7 +32,7 @@ static int dump(u128 start, u64 count, int lo, int hi) {
     if constexpr (P::SIB > 1) {
         constexpr u64 D = (u64)P::B * P::B, SB = (u64)P::SIB * D;
         double rounds = 0;
-        const u64 L = pick_small_stride<P>(start, count, 105, 210, P::LO + 1, count / SB, 262144, D, rounds);
+        const u64 L = pick_small_stride<P>(start, count, 105, 210, P::LO + 1, count / SB, 256 * 1024, D, rounds);
         printf("rounds pick [105, 210]: %llu (%.3f rounds)\n", (unsigned long long)L, rounds);
     }
     return 0;
@@ -44,11 +44,11 @@ int main(int argc, char **argv) {
     const u128 start = parse_u128(argv[2]);
     const u64 count = (u64)atof(argv[3]);
     const int lo = argc > 4 ? atoi(argv[4]) : 61, hi = argc > 5 ? atoi(argv[5]) : 255;
-    if (!strcmp(cfg, "40p")) return dump<Cfg<40, 4, 8, 5, 0, 512, 4097, 100, 0, 3>>(start, count, lo, hi);
-    if (!strcmp(cfg, "40")) return dump<Cfg<40, 5, 8, 5, 0, 512, 0, 1, 0, 3>>(start, count, lo, hi);
-    if (!strcmp(cfg, "42")) return dump<Cfg<42, 5, 9, 5, 0, 512, 0, 1, 0, 3>>(start, count, lo, hi);
-    if (!strcmp(cfg, "44")) return dump<Cfg<44, 5, 9, 5, 0, 512, 0, 1, 0, 3>>(start, count, lo, hi);
-    if (!strcmp(cfg, "50")) return dump<Cfg<50, 5, 10, 6, 0, 512, 0, 1, 0, 2>>(start, count, lo, hi);
+    if (!strcmp(cfg, "40p")) return dump<BigCfg<40, 4, 8, 5>>(start, count, lo, hi);
+    if (!strcmp(cfg, "40")) return dump<BigCfg<40, 5, 8, 5>>(start, count, lo, hi);
+    if (!strcmp(cfg, "42")) return dump<BigCfg<42, 5, 9, 5>>(start, count, lo, hi);
+    if (!strcmp(cfg, "44")) return dump<BigCfg<44, 5, 9, 5>>(start, count, lo, hi);
+    if (!strcmp(cfg, "50")) return dump<BigCfg<50, 5, 10, 6>>(start, count, lo, hi);
     fprintf(stderr, "unknown CFG %s\n", cfg);
     return 2;
 }

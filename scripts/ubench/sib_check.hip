@@ -29,12 +29,12 @@ std::atomic<uint32_t> nice::fd2::g_force_sib_pers[2] = {{0}, {0}};
 #define XNE2 5
 #endif
 // XREF 0: the regular big-field kernel of the base (b40: the round-4
-// kernel); 1: the round-5 production b40 sibling kernel
+// kernel); 1: the production b40 sibling kernel
 #if defined(XREF) && XREF == 1
-using Ref = Cfg<40, 4, 8, 5, 0, 512, 4097, 100, 0, 3>;
+using Ref = BigCfg<40, 4, 8, 5>;
 #elif !defined(XREFVD)
 #define XREF 0
-using Ref = Cfg<XB, XND, XNE, XNE2, 0, big_wg(XB), valu_limbs_big(XB, XND, XNE)>;
+using Ref = RegularBig<XB, XND, XNE, XNE2>;
 #endif
 #ifndef XPERS
 #define XPERS 0

@@ -123,12 +123,12 @@ int main() {
     // the bench field: pick_lane_stride over [105, 210] at target 140, and the
     // lone-field pick over the same range on 262 144 lanes
     {
-        using P = Cfg<40, 4, 8, 5, 0, 512, 4097, 100, 0, 3>;
+        using P = BigCfg<40, 4, 8, 5>;
         const u128 start = 1916284264916ull;
         const u64 count = 1000000000, D = (u64)P::B * P::B, SB = P::SIB * D;
         double rounds = 0;
         printf("P b40_sib3_pipe %llu %llu\n", (ull)pick_lane_stride<P>(start, count, 105, 210, 140, P::LO + 1),
-               (ull)pick_small_stride<P>(start, count, 105, 210, P::LO + 1, count / SB, 262144, D, rounds));
+               (ull)pick_small_stride<P>(start, count, 105, 210, P::LO + 1, count / SB, 256 * 1024, D, rounds));
     }
     char line[128];
     while (fgets(line, sizeof line, stdin)) {
@@ -136,20 +136,21 @@ int main() {
         char num[64];
         if (sscanf(line, "%d %63s", &base, num) != 2) continue;
         const u128 start = parse_u128(num);
-        // configurations fd2_part.hip dispatches to
+        // configurations fd2_part.hip dispatches to (fd2_cfg.hpp: BigCfg for
+        // fields >= 1e7, its NoSib fallback, SmallCfg below)
         if (base == 40) {
-            run_cfg<Cfg<40, 4, 8, 5, 0, 512, 4097, 100, 0, 3>>("b40_sib3_pipe", start);
-            run_cfg<Cfg<40, 5, 8, 5, 0, 512, 0, 1, 0, 3>>("b40_sib3", start);
-            run_cfg<Cfg<40, 4, 8, 5, 0, 512, valu_limbs(40)>>("b40_512", start);
+            run_cfg<BigCfg<40, 4, 8, 5>>("b40_sib3_pipe", start);
+            run_cfg<BigCfg<40, 5, 8, 5>>("b40_sib3", start);
+            run_cfg<SmallCfg<40, 4, 8, 5>>("b40_512", start);
         } else if (base == 44) {
-            run_cfg<Cfg<44, 5, 9, 5, 0, 512, 0, 1, 0, 3>>("b44_sib3", start);
+            run_cfg<BigCfg<44, 5, 9, 5>>("b44_sib3", start);
         } else if (base == 52) {
-            run_cfg<Cfg<52, 6, 11, 6, 0, 512, 0, 1, 0, 2>>("b52_sib2", start);
+            run_cfg<BigCfg<52, 6, 11, 6>>("b52_sib2", start);
         } else if (base == 50) {
-            run_cfg<Cfg<50, 5, 10, 6, 0, big_wg(50), valu_limbs_big(50, 5, 10)>>("b50_big", start);
+            run_cfg<BigCfg<50, 5, 10, 6>::NoSib>("b50_big", start);
         } else if (base == 80) {
-            run_cfg<Cfg<80, 8, 16, 9, 0, big_wg(80), valu_limbs_big(80, 8, 16)>>("b80_big", start);
-            run_cfg<Cfg<80, 8, 16, 9, 0, 512, valu_limbs(80)>>("b80_512", start);
+            run_cfg<BigCfg<80, 8, 16, 9>>("b80_big", start);
+            run_cfg<SmallCfg<80, 8, 16, 9>>("b80_512", start);
         }
     }
     return 0;

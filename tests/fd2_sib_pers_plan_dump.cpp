@@ -29,7 +29,7 @@ using namespace nice;
 using namespace nice::fd2;
 
 typedef unsigned long long ull;
-using P = Cfg<40, 4, 8, 5, 0, 512, 4097, 100, 0, 3>;
+using P = BigCfg<40, 4, 8, 5>;  // production: the pipelined b40 sibling kernel
 static_assert(P::HAS_SIBPERS && P::SibPers::SIBPERS && !P::SibPers::PERS && P::SibPers::WG == P::WG &&
                   P::SibPers::LDS_BYTES == P::LDS_BYTES,
               "the persistent twin shares the rounds kernel's layout");

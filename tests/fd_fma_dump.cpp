@@ -131,9 +131,9 @@ static void run() {
 }
 
 int main() {
-    // the low-digit-table mode of the base (VD & 1024) kept, as fd2_part.hip's
+    // the low-digit-table mode of the base (vd::SIDE) kept, as fd2_part.hip's
     // configurations keep it; the flag on
-#define X(B_, ND_, NE_, NE2_) run<Cfg<B_, ND_, NE_, NE2_, 0, 512, (valu_limbs(B_) & 1024) | 262144>>();
+#define X(B_, ND_, NE_, NE2_) run<Cfg<B_, ND_, NE_, NE2_, 0, 512, (valu_limbs(B_) & vd::SIDE) | vd::FMA>>();
     FD2_COMBOS(X)
 #undef X
     return 0;
