@@ -459,7 +459,9 @@ int nice_debug_ranges_plan(uint32_t base, const uint64_t *bounds, size_t n_range
  * (b - 1) * b^k table with k = stride_k, 0 meaning 2 -- gets the full test,
  * which is the contract of the reference's niceonly_ranges_kernel
  * (nice_kernels.cu:420-470): the caller did the filtering.  So there is no
- * filter option; Filter C and the sound prefix test belong to the MSD recursion.
+ * filter option: Filter C belongs to the MSD recursion.  The sound filter's
+ * per-candidate prefix test does run on a caller's ranges, through
+ * nice_process_ranges_niceonly_ex below.
  *   candidates[i] (may be null): the stride candidates in range i.
  *   square_ok[i] (may be null): how many of them have a repeat-free square,
  *     counted where the field path counts it -- a nice_niceonly_fast_base, the
@@ -500,7 +502,72 @@ typedef struct {
     double kernel_ms;        /* HIP events around the launches (the slowest device) */
 } nice_ranges_niceonly_stats;
 int nice_last_ranges_niceonly_stats(nice_ctx *ctx, nice_ranges_niceonly_stats *out);
-/* The same on the host cores (no device): the stride walk of
+
+/* nice_process_ranges_niceonly with options: the sound filter's per-candidate
+ * prefix test (NICE_FILTER_SOUND above) per caller range, so that
+ * nice_msd_ranges(..., NICE_FILTER_SOUND) composed with this call tests what a
+ * device-MSD sound field tests.
+ * The rule needs no recursion: for any range [s, e) of >= 2 numbers inside a
+ * base's valid range every n has n^2 beginning with the common leading digits
+ * of s^2 and (e - 1)^2 (P2; none when their digit counts differ) and n^3 with
+ * those of the two cubes (P3).  With L the two lowest digits of n^2 and of n^3,
+ * n is rejected iff the list P2 + P3 + L holds a repeated value -- then n^2 or
+ * n^3 repeats a digit, or they share one, so no rejected n is nice.  A range of
+ * one number rejects nothing.
+ * prefix_test = NICE_RANGES_PREFIX_ON runs it exactly where the field path runs
+ * it: a nice_niceonly_fast_base, the k = 2 table, the range wholly inside the
+ * valid range (the ranges nice_ranges_niceonly_stats.fast_ranges counts).
+ * There a mask kernel makes each range's digit mask of P2 + P3 in a launch of
+ * its own before the candidate launch, whose prefix-testing variant rejects
+ * candidates ahead of the square test.  Every other range is tested as
+ * nice_process_ranges_niceonly tests it.
+ *   candidates[i]: unchanged, every stride candidate of range i.
+ *   prefix_rejected[i] (may be null): the candidates of range i the rule
+ *     rejects; 0 for a range the test does not run on.
+ *   square_ok[i]: the KEPT candidates with a repeat-free square (the sound
+ *     field's square_ok).
+ *   the list: the kept candidates that pass -- in production the list of the
+ *     call with the test off; under nice_debug_set_nice_min the kept square
+ *     survivors with a union count >= nice_min.
+ * prefix_test = NICE_RANGES_PREFIX_OFF, or opts null (all zero): bit for bit
+ * nice_process_ranges_niceonly (prefix_rejected all zero).  Any other value:
+ * NICE_ERR_INVALID, as are non-zero reserved words.  Limits, errors, locking,
+ * device dealing and the capacity retry (the kept results include
+ * prefix_rejected) are nice_process_ranges_niceonly's; both calls share the
+ * kept results, so a retry must repeat the options too. */
+#define NICE_RANGES_PREFIX_OFF 0
+#define NICE_RANGES_PREFIX_ON 1
+typedef struct {
+    uint32_t stride_k;    /* 0: 2 */
+    uint32_t prefix_test; /* NICE_RANGES_PREFIX_* */
+    uint32_t reserved[2]; /* zero */
+} nice_ranges_niceonly_opts;
+int nice_process_ranges_niceonly_ex(nice_ctx *ctx, uint32_t base, const uint64_t *bounds,
+                                    size_t n_ranges, const nice_ranges_niceonly_opts *opts,
+                                    uint64_t *candidates, uint32_t *square_ok,
+                                    uint64_t *prefix_rejected, nice_number *out,
+                                    uint32_t *out_range, size_t cap, size_t *n_out);
+/* The prefix test's part of the last call that ran (all zero when it was off;
+ * nice_last_ranges_niceonly_stats describes the candidate launches as before,
+ * its kernel_ms spanning the mask launch too). */
+typedef struct {
+    uint32_t prefix_ranges; /* ranges the test ran on */
+    uint32_t launches;      /* mask-kernel launches: one per device that had such ranges */
+    uint64_t rejected;      /* prefix_rejected summed over the ranges */
+    double mask_ms;         /* HIP events around the mask launch (the slowest device) */
+} nice_ranges_niceonly_prefix_stats;
+int nice_last_ranges_niceonly_prefix(nice_ctx *ctx, nice_ranges_niceonly_prefix_stats *out);
+/* nice_process_ranges_niceonly_ex on the host cores (no device), `threads`
+ * instead of ctx.  The test runs on the same ranges as on the GPU, so
+ * prefix_rejected equals the GPU's; square_ok is counted for every range (for
+ * the kept candidates where the test ran). */
+int nice_cpu_process_ranges_niceonly_ex(uint32_t base, const uint64_t *bounds, size_t n_ranges,
+                                        const nice_ranges_niceonly_opts *opts, int32_t threads,
+                                        uint64_t *candidates, uint32_t *square_ok,
+                                        uint64_t *prefix_rejected, nice_number *out,
+                                        uint32_t *out_range, size_t cap, size_t *n_out);
+
+/* nice_process_ranges_niceonly on the host cores (no device): the stride walk of
  * stride_filter.rs:139-155 over each range with get_is_nice, the ranges spread
  * over `threads`.  square_ok is counted for every range. */
 int nice_cpu_process_ranges_niceonly(uint32_t base, const uint64_t *bounds, size_t n_ranges,

@@ -12,7 +12,7 @@ from .api import (CLIENT_VERSION, GPU_BATCH_SIZE, PROCESSING_CHUNK_SIZE, BothMod
                   process_range_detailed_gpu, process_range_niceonly,
                   process_range_niceonly_gpu, process_range_detailed_cpu,
                   process_range_niceonly_cpu, process_ranges_detailed_gpu,
-                  process_ranges_detailed_cpu, niceonly_ranges_cpu, process_ranges_niceonly_gpu,
+                  process_ranges_detailed_cpu, niceonly_ranges_cpu, niceonly_ranges_ex_cpu, process_ranges_niceonly_gpu,
                   process_ranges_niceonly_cpu, unique_map_cpu, RangeBounds, chunk_roots, msd_ranges_cpu,
                   msd_ranges_plan)
 from .survey import class_distribution, survey_base, survey_niceonly_base  # noqa: F401

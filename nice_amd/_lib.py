@@ -28,6 +28,8 @@ NICE_MSD_FLOOR_ADAPTIVE = (1 << 64) - 1  # msd_floor: the reference GPU path's A
 # (no Filter C; a per-candidate prefix test instead, see include/nice_hip.h)
 NICE_FILTER_REFERENCE = 0
 NICE_FILTER_SOUND = 1
+NICE_RANGES_PREFIX_OFF = 0
+NICE_RANGES_PREFIX_ON = 1
 # nice_process_ranges_detailed flags: one histogram row per range, or their sum
 NICE_RANGES_PER_RANGE = 0
 NICE_RANGES_SUM = 1
@@ -56,6 +58,7 @@ EXPORTS = (
     "nice_debug_set_nice_min", "nice_debug_cube_count", "nice_debug_force_sib_persistent",
     "nice_process_ranges_niceonly", "nice_last_ranges_niceonly_stats", "nice_cpu_process_ranges_niceonly",
     "nice_debug_ranges_niceonly_plan",
+    "nice_process_ranges_niceonly_ex", "nice_cpu_process_ranges_niceonly_ex", "nice_last_ranges_niceonly_prefix",
     "nice_unique_map", "nice_cpu_unique_map", "nice_last_map_stats", "nice_debug_map_plan",
     "nice_msd_ranges", "nice_cpu_msd_ranges", "nice_last_msd_ranges_stats", "nice_debug_msd_ranges_plan",
 )
@@ -108,6 +111,16 @@ class nice_ranges_niceonly_stats(ctypes.Structure):
                 ("generic_ranges", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("candidates", ctypes.c_uint64), ("square_ok", ctypes.c_uint64),
                 ("kernel_ms", ctypes.c_double)]
+
+
+class nice_ranges_niceonly_opts(ctypes.Structure):
+    _fields_ = [("stride_k", ctypes.c_uint32), ("prefix_test", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+class nice_ranges_niceonly_prefix_stats(ctypes.Structure):
+    _fields_ = [("prefix_ranges", ctypes.c_uint32), ("launches", ctypes.c_uint32),
+                ("rejected", ctypes.c_uint64), ("mask_ms", ctypes.c_double)]
 
 
 class nice_map_stats(ctypes.Structure):
@@ -210,6 +223,11 @@ def lib():
         "nice_last_ranges_niceonly_stats": ([vp, ctypes.POINTER(nice_ranges_niceonly_stats)], i32),
         "nice_cpu_process_ranges_niceonly": ([u32, P64, sz, u32, i32, P64, P32, PN, P32, sz, PSZ], i32),
         "nice_debug_ranges_niceonly_plan": ([u32, u32, P64, sz, u32, P64, sz, PSZ], i32),
+        "nice_process_ranges_niceonly_ex": ([vp, u32, P64, sz, ctypes.POINTER(nice_ranges_niceonly_opts), P64, P32,
+                                             P64, PN, P32, sz, PSZ], i32),
+        "nice_cpu_process_ranges_niceonly_ex": ([u32, P64, sz, ctypes.POINTER(nice_ranges_niceonly_opts), i32, P64,
+                                                 P32, P64, PN, P32, sz, PSZ], i32),
+        "nice_last_ranges_niceonly_prefix": ([vp, ctypes.POINTER(nice_ranges_niceonly_prefix_stats)], i32),
         # `out` as an address: a numpy buffer's or a torch tensor's data_ptr()
         "nice_unique_map": ([vp, u64, u64, u64, u64, u32, vp, sz, u32, i32], i32),
         "nice_cpu_unique_map": ([u64, u64, u64, u64, u32, i32, vp, sz], i32),

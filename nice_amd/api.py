@@ -205,6 +205,14 @@ class RangesNiceonlyStats:
 
 
 @dataclass
+class RangesNiceonlyPrefixStats:
+    prefix_ranges: int   # ranges the prefix test ran on
+    launches: int        # mask-kernel launches (one per device that had such ranges)
+    rejected: int        # candidates the test rejected, summed over the ranges
+    mask_ms: float       # HIP events around the mask launch (the slowest device)
+
+
+@dataclass
 class MsdRangesStats:
     launches: int     # recursion kernel launches of the call (the sort's not counted)
     fused_roots: int  # roots run one workgroup per root
@@ -479,6 +487,31 @@ class GpuContext:
         return _niceonly_ranges_call(
             lambda *a: lib().nice_process_ranges_niceonly(self._h, base, bounds, n_ranges, stride_k, *a),
             n_ranges, cap)
+
+    def niceonly_ranges_ex(self, ranges, base: int, stride_k: int = 0, prefix_test: bool = False, cap: int = 0):
+        """niceonly_ranges with options (nice_process_ranges_niceonly_ex).
+        prefix_test=True runs the sound filter's per-candidate prefix test per
+        range, where the field path runs it (a niceonly fast base, k = 2, the
+        range inside the valid range): a mask kernel makes each range's mask
+        of the common leading digits of n^2 and n^3, and the candidate kernel
+        rejects against it ahead of the square test.  Returns (candidates,
+        square_ok, prefix_rejected, [(n, range_index)]): candidates as
+        niceonly_ranges counts them, prefix_rejected the rejected ones per
+        range (0 where the test does not run), square_ok the KEPT candidates
+        with a repeat-free square, the list the kept candidates that pass.
+        prefix_test=False is niceonly_ranges with an all-zero third list.
+        See ranges_niceonly_stats() and ranges_niceonly_prefix_stats()."""
+        bounds, n_ranges = _pack_ranges(ranges)
+        opts = _ranges_niceonly_opts(stride_k, prefix_test)
+        return _niceonly_ranges_ex_call(
+            lambda *a: lib().nice_process_ranges_niceonly_ex(self._h, base, bounds, n_ranges, opts, *a),
+            n_ranges, cap)
+
+    def ranges_niceonly_prefix_stats(self) -> "RangesNiceonlyPrefixStats":
+        """The prefix test's part of this context's last niceonly_ranges(_ex) call."""
+        s = _lib.nice_ranges_niceonly_prefix_stats()
+        check(lib().nice_last_ranges_niceonly_prefix(self._h, s))
+        return RangesNiceonlyPrefixStats(s.prefix_ranges, s.launches, s.rejected, s.mask_ms)
 
     def ranges_niceonly_stats(self) -> "RangesNiceonlyStats":
         """Statistics of this context's last niceonly_ranges call."""
@@ -803,6 +836,36 @@ def niceonly_ranges_cpu(ranges, base: int, stride_k: int = 0, threads: int = 1, 
     bounds, n_ranges = _pack_ranges(ranges)
     return _niceonly_ranges_call(
         lambda *a: lib().nice_cpu_process_ranges_niceonly(base, bounds, n_ranges, stride_k, threads, *a),
+        n_ranges, cap)
+
+
+def _ranges_niceonly_opts(stride_k: int, prefix_test):
+    # (an integer passes through as it is, so that the library judges it)
+    pt = int(prefix_test) if not isinstance(prefix_test, bool) else (
+        _lib.NICE_RANGES_PREFIX_ON if prefix_test else _lib.NICE_RANGES_PREFIX_OFF)
+    return _lib.nice_ranges_niceonly_opts(stride_k, pt)
+
+
+def _niceonly_ranges_ex_call(call, n_ranges: int, cap: int):
+    """call(candidates, square_ok, prefix_rejected, out, out_range, cap, n_out)
+    -> rc, retried with room on NICE_ERR_CAPACITY."""
+    cand = (ctypes.c_uint64 * max(n_ranges, 1))()
+    sq = (ctypes.c_uint32 * max(n_ranges, 1))()
+    rej = (ctypes.c_uint64 * max(n_ranges, 1))()
+    (out, idx), n = _with_room(lambda *a: call(cand, sq, rej, *a), max(cap, 1024), _list_bufs)
+    return (list(cand[:n_ranges]), list(sq[:n_ranges]), list(rej[:n_ranges]),
+            [(out[i].number_lo | (out[i].number_hi << 64), idx[i]) for i in range(n)])
+
+
+def niceonly_ranges_ex_cpu(ranges, base: int, stride_k: int = 0, prefix_test: bool = False, threads: int = 1,
+                           cap: int = 0):
+    """GpuContext.niceonly_ranges_ex on the host cores
+    (nice_cpu_process_ranges_niceonly_ex): no device.  The prefix test runs on
+    the same ranges as on the GPU; square_ok is counted for every range."""
+    bounds, n_ranges = _pack_ranges(ranges)
+    opts = _ranges_niceonly_opts(stride_k, prefix_test)
+    return _niceonly_ranges_ex_call(
+        lambda *a: lib().nice_cpu_process_ranges_niceonly_ex(base, bounds, n_ranges, opts, threads, *a),
         n_ranges, cap)
 
 

@@ -87,6 +87,9 @@ def parse_args(argv=None):
     p.add_argument("--survey-msd", choices=("host", "device"), default="host",
                    help="--survey-niceonly: where the windows' MSD filter runs -- the host recursion per "
                         "window, or (with --gpu) one device range-list call per filter (GpuContext.msd_ranges)")
+    p.add_argument("--survey-prefix", action="store_true",
+                   help="--survey-niceonly: run the sound filter's per-candidate prefix test on the sound "
+                        "column's ranges too (prefix_rejected; square_ok then counts the kept candidates)")
     p.add_argument("--survey-classes", type=int, default=None, metavar="M",
                    help="survey --base by residue class: the table [n mod M][num_uniques] of the same "
                         "stratified windows, from the per-number map (nice_amd/survey.py class_distribution); "
@@ -245,7 +248,8 @@ def run_survey_niceonly(args, ctx) -> int:
     floor = args.msd_floor or 250
     t0 = time.perf_counter()
     r = survey_niceonly_base(ctx, args.base, args.windows, args.window_size, args.seed, floor,
-                             threads=max(1, args.threads), msd_where=args.survey_msd)
+                             threads=max(1, args.threads), msd_where=args.survey_msd,
+                             prefix_test=args.survey_prefix)
     elapsed = time.perf_counter() - t0
     log.info("✓ Surveyed %.2e numbers of base %d for niceonly in %.2fs", r.sampled, args.base, elapsed)
     out = {"base": r.base, "windows": len(r.windows), "window_size": args.window_size, "seed": args.seed,

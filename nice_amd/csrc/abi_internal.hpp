@@ -278,13 +278,25 @@ struct RangesNiceDev {
     uint32_t *h_count = nullptr, *d_count_mapped = nullptr;  // mapped: the list count at a launch's end
     ListBuf list;               // list.u: the entries' range indices
     std::map<uint32_t, uint32_t *> residues;  // base*8+k -> device residue table
+    // the prefix test (nice_process_ranges_niceonly_ex), allocated on its first use
+    std::map<uint32_t, uint32_t *> lowtabs;  // base*8+k -> residues_flagged followed by lowmask
+    StagePair spans;                         // RangeSpan records, one per fast range of the share
+    LeafMask *d_masks = nullptr;             // ... and their masks (range_mask_kernel)
+    size_t masks_cap = 0;
+    unsigned long long *d_rej = nullptr;     // prefix_rejected, one counter per range
+    size_t rej_cap = 0;
+    hipEvent_t ev_mask = nullptr;            // after the mask launch (side.ev0 before it)
 };
-struct RangesNiceState : KeptList {  // key: the stride k; Entry::u: the range index
+// key: the stride k, plus kRangesPrefixKey with the prefix test on; Entry::u: the range index
+constexpr uint32_t kRangesPrefixKey = 1u << 8;
+struct RangesNiceState : KeptList {
     std::vector<RangesNiceDev> dev;
     nice_ranges_niceonly_stats stats{};
+    nice_ranges_niceonly_prefix_stats prefix{};
     uint32_t nice_min = 0;
     std::vector<uint64_t> candidates;
     std::vector<uint32_t> square_ok;
+    std::vector<uint64_t> prefix_rejected;
 };
 
 struct MapDev {

@@ -133,19 +133,62 @@ bool square_free(u128 n, const BP &bp) {
 struct RangeAnswer {
     uint64_t candidates = 0;
     uint32_t square_ok = 0;
+    uint64_t prefix_rejected = 0;
     std::vector<u128> nice;
 };
+
+// The sound filter's prefix mask of the range [s, e) of >= 2 numbers, by the
+// digits themselves (no limb path: the device's msd_prefix_masks is checked
+// against this): the digit mask of P2 + P3, the common leading digits of
+// s^2, (e - 1)^2 and of the two cubes (none where the digit counts differ);
+// all ones when P2 + P3 itself holds a repeat.
 template <class BP>
-void niceonly_range_counted(u128 s, u128 e, const BP &bp, const nice::StrideTable &t, RangeAnswer &out) {
+void range_prefix_mask(u128 s, u128 e, const BP &bp, uint32_t pm[4]) {
+    typedef nice::MsdFilterT<BP> F;
+    uint32_t fsq[8], fcu[12], lsq[8], lcu[12];
+    F::powers(s, fsq, fcu);
+    F::powers(e - 1, lsq, lcu);
+    nice::DigitBuf a, b;
+    Bits seen;
+    bool dup = false;
+    auto common = [&] {
+        if (a.n != b.n) return;
+        const int c = F::common_msd(a, b);
+        for (int i = 0; i < c; i++) dup |= !seen.add(a.d[a.n - 1 - i]);
+    };
+    nice::digits_of(fsq, 8, bp, a);
+    nice::digits_of(lsq, 8, bp, b);
+    common();
+    nice::digits_of(fcu, 12, bp, a);
+    nice::digits_of(lcu, 12, bp, b);
+    common();
+    for (int w = 0; w < 4; w++) pm[w] = dup ? ~0u : (uint32_t)(seen.w[w / 2] >> (32 * (w % 2)));
+}
+
+// Candidates [g0, g1) of the residue sequence, all inside the range [s, e).
+// prefix: the range is one the prefix test runs on (nice_range_fast, the test
+// asked for): a rejected candidate is counted and goes no further.
+template <class BP>
+void niceonly_range_counted(u128 s, u128 e, u128 g0, u128 g1, const BP &bp, const nice::StrideTable &t, bool prefix,
+                            RangeAnswer &out) {
     const size_t R = t.residues.size();
     const u128 M = t.modulus;
-    const u128 i0 = t.index_of(s), i1 = t.index_of(e);
-    u128 cyc = i0 / R;
-    size_t r = (size_t)(i0 - cyc * R);
-    out.candidates = (uint64_t)(i1 - i0);
-    for (u128 g = i0; g < i1; g++) {
+    u128 cyc = g0 / R;
+    size_t r = (size_t)(g0 - cyc * R);
+    const int mw = (int)(bp.b + 31) / 32;
+    const uint32_t multi = e - s > 1 ? 1u : 0u;
+    uint32_t pm[4] = {0, 0, 0, 0};
+    if (prefix && multi && g1 > g0) range_prefix_mask(s, e, bp, pm);
+    for (u128 g = g0; g < g1; g++) {
         const u128 n = cyc * M + t.residues[r];
-        if (square_free(n, bp)) {
+        bool gone = false;
+        if (prefix) {  // radix_fast.hpp prefix_rejects
+            for (int w = 0; w < mw; w++) gone |= (pm[w] & t.lowmask[r * mw + w]) != 0;
+            gone |= multi && (t.residues_flagged[r] & nice::StrideTable::kLowDup);
+        }
+        if (gone) {
+            out.prefix_rejected++;
+        } else if (square_free(n, bp)) {
             out.square_ok++;
             if (is_nice(n, bp)) out.nice.push_back(n);
         }
@@ -158,19 +201,46 @@ void niceonly_range_counted(u128 s, u128 e, const BP &bp, const nice::StrideTabl
 
 int nthreads(int threads, u128 work);
 
+// The ranges spread over the threads in pieces of at most kCpuPiece candidates
+// (a range of 2^28 candidates would otherwise keep one thread busy alone); a
+// range's pieces are added up in ascending order.
+constexpr uint64_t kCpuPiece = 1u << 20;
+
 template <class BP>
 void ranges_niceonly_cpu(const BP &bp, const nice::StrideTable &t, const uint64_t *bounds, size_t n_ranges,
-                         int threads, std::vector<RangeAnswer> &ans) {
+                         uint32_t k, bool prefix, int threads, std::vector<RangeAnswer> &ans) {
+    struct Work {
+        size_t range;
+        u128 g0, g1;
+        RangeAnswer part;
+    };
+    std::vector<Work> work;
+    for (size_t i = 0; i < n_ranges; i++) {
+        const u128 i0 = t.index_of(nice::range_at(bounds, i, 0)), i1 = t.index_of(nice::range_at(bounds, i, 1));
+        ans[i].candidates = (uint64_t)(i1 - i0);
+        for (u128 g = i0; g < i1; g += kCpuPiece) work.push_back(Work{i, g, std::min<u128>(g + kCpuPiece, i1), {}});
+    }
     std::atomic<size_t> next{0};
     auto run = [&] {
-        for (size_t i; (i = next.fetch_add(1)) < n_ranges;)
-            niceonly_range_counted(nice::range_at(bounds, i, 0), nice::range_at(bounds, i, 1), bp, t, ans[i]);
+        for (size_t q; (q = next.fetch_add(1)) < work.size();) {
+            Work &w = work[q];
+            const u128 s = nice::range_at(bounds, w.range, 0), e = nice::range_at(bounds, w.range, 1);
+            // the test's domain is the GPU call's: the ranges its plan calls fast
+            const bool pre = prefix && !t.lowmask.empty() && nice::nice_range_fast(bp.b, k, s, e);
+            niceonly_range_counted(s, e, w.g0, w.g1, bp, t, pre, w.part);
+        }
     };
-    const int nt = nthreads(threads, n_ranges);
+    const int nt = nthreads(threads, work.size());
     std::vector<std::thread> ws;
     for (int i = 0; i + 1 < nt; i++) ws.emplace_back(run);
     run();  // the caller's thread
     for (auto &w : ws) w.join();
+    for (const Work &w : work) {
+        RangeAnswer &a = ans[w.range];
+        a.square_ok += w.part.square_ok;
+        a.prefix_rejected += w.part.prefix_rejected;
+        a.nice.insert(a.nice.end(), w.part.nice.begin(), w.part.nice.end());
+    }
 }
 
 int nthreads(int threads, u128 work) {
@@ -350,14 +420,20 @@ extern "C" int nice_cpu_process_ranges_detailed(uint32_t base, const uint64_t *b
     return NICE_OK;
 }
 
-// nice_process_ranges_niceonly on the host cores: no MSD filter, every stride
-// candidate of every range (stride_filter.rs:139-155) through get_is_nice.
-extern "C" int nice_cpu_process_ranges_niceonly(uint32_t base, const uint64_t *bounds, size_t n_ranges,
-                                                uint32_t stride_k, int32_t threads, uint64_t *candidates,
-                                                uint32_t *square_ok, nice_number *out, uint32_t *out_range,
-                                                size_t cap, size_t *n_out) {
+// nice_process_ranges_niceonly_ex on the host cores: no MSD filter, every stride
+// candidate of every range (stride_filter.rs:139-155) through get_is_nice --
+// with the prefix test on, after that test on the ranges the GPU call runs it on.
+extern "C" int nice_cpu_process_ranges_niceonly_ex(uint32_t base, const uint64_t *bounds, size_t n_ranges,
+                                                   const nice_ranges_niceonly_opts *opts, int32_t threads,
+                                                   uint64_t *candidates, uint32_t *square_ok,
+                                                   uint64_t *prefix_rejected, nice_number *out, uint32_t *out_range,
+                                                   size_t cap, size_t *n_out) {
     if (!bounds || !n_out || (cap && !out)) return cpu_fail(NICE_ERR_INVALID, "null argument");
-    const uint32_t k = stride_k ? stride_k : 2;
+    const nice_ranges_niceonly_opts o = opts ? *opts : nice_ranges_niceonly_opts{};
+    if (o.prefix_test > NICE_RANGES_PREFIX_ON)
+        return cpu_fail(NICE_ERR_INVALID, "prefix_test must be NICE_RANGES_PREFIX_OFF or NICE_RANGES_PREFIX_ON");
+    if (o.reserved[0] || o.reserved[1]) return cpu_fail(NICE_ERR_INVALID, "reserved option words must be zero");
+    const uint32_t k = o.stride_k ? o.stride_k : 2;
     if (const char *why = nice::nice_ranges_check(base, n_ranges, k)) return cpu_fail(NICE_ERR_INVALID, why);
     for (size_t i = 0; i < n_ranges; i++)
         if (nice::range_at(bounds, i, 0) >= nice::range_at(bounds, i, 1))
@@ -373,7 +449,8 @@ extern "C" int nice_cpu_process_ranges_niceonly(uint32_t base, const uint64_t *b
                                     ("range " + std::to_string(i) + " holds more than 2^40 candidates: use a field")
                                         .c_str());
             with_base(base, [&](const auto &bp) {
-                ranges_niceonly_cpu(bp, table, bounds, n_ranges, threads, ans);
+                ranges_niceonly_cpu(bp, table, bounds, n_ranges, k, o.prefix_test == NICE_RANGES_PREFIX_ON, threads,
+                                    ans);
                 return 0;
             });
         }
@@ -382,6 +459,7 @@ extern "C" int nice_cpu_process_ranges_niceonly(uint32_t base, const uint64_t *b
     for (size_t i = 0; i < n_ranges; i++) {
         if (candidates) candidates[i] = ans[i].candidates;
         if (square_ok) square_ok[i] = ans[i].square_ok;
+        if (prefix_rejected) prefix_rejected[i] = ans[i].prefix_rejected;
         total += ans[i].nice.size();
     }
     *n_out = total;
@@ -394,6 +472,15 @@ extern "C" int nice_cpu_process_ranges_niceonly(uint32_t base, const uint64_t *b
             q++;
         }
     return NICE_OK;
+}
+
+extern "C" int nice_cpu_process_ranges_niceonly(uint32_t base, const uint64_t *bounds, size_t n_ranges,
+                                                uint32_t stride_k, int32_t threads, uint64_t *candidates,
+                                                uint32_t *square_ok, nice_number *out, uint32_t *out_range,
+                                                size_t cap, size_t *n_out) {
+    const nice_ranges_niceonly_opts o{stride_k, NICE_RANGES_PREFIX_OFF, {0, 0}};
+    return nice_cpu_process_ranges_niceonly_ex(base, bounds, n_ranges, &o, threads, candidates, square_ok, nullptr,
+                                               out, out_range, cap, n_out);
 }
 
 // nice_msd_ranges on the host cores: the host recursion root by root.

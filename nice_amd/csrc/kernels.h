@@ -186,7 +186,8 @@ struct RangeLeaf {
     uint64_t b0_lo, b0_hi;  // as Leaf
     uint32_t g0, count;
     uint32_t range;         // range index of the call
-    uint32_t pad;
+    uint32_t mask;          // prefix test: the range's index among the launch's RangeSpan / LeafMask
+                            // records (every piece of a range carries the same one); else 0
 };
 struct NiceRangesLaunch {
     NiceonlyLaunch c;          // residues, R, M, base, in_range, nice_min and out, where out.u receives
@@ -197,9 +198,30 @@ struct NiceRangesLaunch {
     uint32_t *done;            // kDoneWords arrival counters, re-zeroed by the last workgroup
     uint32_t *count_mapped;    // ... which copies *c.out.count here (mapped host memory)
 };
+// The sound filter's per-candidate prefix test on caller-given ranges
+// (nice_process_ranges_niceonly_ex, NICE_RANGES_PREFIX_ON): a range [first,
+// last] of a fast base, inside its valid range, has a LeafMask of its own --
+// every n of it carries the common leading digits of first^2, last^2 and of
+// the two cubes -- made by range_mask_kernel from a RangeSpan before the
+// candidate launch, whose prefix variant tests each candidate's residue
+// against it ahead of the square test.
+struct RangeSpan {
+    uint64_t first_lo, first_hi;  // the range's first number
+    uint64_t last_lo, last_hi;    // ... and its last (end - 1)
+};
+struct RangesPrefixLaunch {
+    SoundLaunch snd;               // residues (flagged) and lowmask; the other fields unused
+    const LeafMask *masks;         // indexed by RangeLeaf::mask
+    unsigned long long *rejected;  // one counter per range of the call
+};
 // c.in_range set: the compile-time kernel of c.base (a niceonly fast base, every
-// leaf inside its valid range); else the run-time-base kernel.
-hipError_t launch_niceonly_ranges(const NiceRangesLaunch &p, int num_cus, hipStream_t s);
+// leaf inside its valid range); else the run-time-base kernel.  pre (in_range
+// launches only): the kernel's prefix-testing variant.
+hipError_t launch_niceonly_ranges(const NiceRangesLaunch &p, int num_cus, hipStream_t s,
+                                  const RangesPrefixLaunch *pre = nullptr);
+// masks[i] = the LeafMask of spans[i], i < n, one lane per span (base: a
+// niceonly fast base, every span inside its valid range).
+hipError_t launch_range_masks(uint32_t base, const RangeSpan *spans, uint32_t n, LeafMask *masks, hipStream_t s);
 
 struct MsdLaunch;
 // Whether a device-MSD field (bounds, base, table and in_range set) can run the

@@ -150,10 +150,17 @@ class NiceonlyFilterSurvey:
     candidates: int      # their stride candidates (k = 2)
     square_ok: int       # ... with a repeat-free square
     found: List[int]     # the numbers that passed, window by window
+    # survey_niceonly_base(prefix_test=True), the sound column: the candidates
+    # the per-candidate prefix test rejected; square_ok then counts the kept ones
+    prefix_rejected: int = 0
+    with_prefix: bool = False  # the survey was asked for the prefix test: counts() shows prefix_rejected
 
     def counts(self) -> dict:
-        return {"msd_ranges": self.msd_ranges, "msd_numbers": self.msd_numbers, "candidates": self.candidates,
-                "square_ok": self.square_ok, "found": len(self.found)}
+        out = {"msd_ranges": self.msd_ranges, "msd_numbers": self.msd_numbers, "candidates": self.candidates,
+               "square_ok": self.square_ok, "found": len(self.found)}
+        if self.with_prefix:
+            out["prefix_rejected"] = self.prefix_rejected
+        return out
 
 
 @dataclass
@@ -182,10 +189,22 @@ def _msd_ranges(window, base, floor, filt):
             for r in api.get_valid_ranges(api.FieldSize(s, e), base, floor, filt)]
 
 
-def _device_filter_survey(ctx, w, base, floor, filt) -> NiceonlyFilterSurvey:
+def _niceonly_batch(ctx, part, base, threads, prefix):
+    """(candidates, square_ok, prefix_rejected, found) of one batched call."""
+    if prefix:
+        c, q, rej, lst = (api.niceonly_ranges_ex_cpu(part, base, prefix_test=True, threads=threads) if ctx is None
+                          else ctx.niceonly_ranges_ex(part, base, prefix_test=True))
+    else:
+        c, q, lst = (api.niceonly_ranges_cpu(part, base, threads=threads) if ctx is None
+                     else ctx.niceonly_ranges(part, base))
+        rej = ()
+    return sum(c), sum(q), sum(rej), [n for n, _ in lst]
+
+
+def _device_filter_survey(ctx, w, base, floor, filt, prefix=False) -> NiceonlyFilterSurvey:
     """One filter's column with the MSD recursion on the device: the windows
     are the roots of ctx.msd_ranges, its bounds the ranges of niceonly_ranges."""
-    n_ranges = numbers = cand = sq = 0
+    n_ranges = numbers = cand = sq = rej = 0
     found: List[int] = []
     for i in range(0, len(w), NICEONLY_BATCH):
         bounds, _ = ctx.msd_ranges(w[i:i + NICEONLY_BATCH], base, floor, filt)
@@ -193,16 +212,15 @@ def _device_filter_survey(ctx, w, base, floor, filt) -> NiceonlyFilterSurvey:
         numbers += bounds.numbers()
         for j in range(0, len(bounds), NICEONLY_BATCH):
             part = bounds if len(bounds) <= NICEONLY_BATCH else bounds.part(j, j + NICEONLY_BATCH)
-            c, q, lst = ctx.niceonly_ranges(part, base)
-            cand += sum(c)
-            sq += sum(q)
-            found += [n for n, _ in lst]
-    return NiceonlyFilterSurvey(filt, n_ranges, numbers, cand, sq, found)
+            c, q, r, f = _niceonly_batch(ctx, part, base, 1, prefix)
+            cand, sq, rej, found = cand + c, sq + q, rej + r, found + f
+    return NiceonlyFilterSurvey(filt, n_ranges, numbers, cand, sq, found, rej, prefix)
 
 
 def survey_niceonly_base(ctx: Optional[api.GpuContext], base: int, windows: int = 4096,
                          window_size: int = 10 ** 6, seed: int = 0, msd_floor: int = 250,
-                         threads: int = 1, msd_where: str = "host") -> NiceonlySurveyResult:
+                         threads: int = 1, msd_where: str = "host",
+                         prefix_test: bool = False) -> NiceonlySurveyResult:
     """What a niceonly search of `base` would cost, from the stratified windows
     of survey_windows.  Per window the MSD filter (nice_msd_valid_ranges_ex,
     floor msd_floor) runs on `threads` host threads, once under the reference
@@ -220,8 +238,13 @@ def survey_niceonly_base(ctx: Optional[api.GpuContext], base: int, windows: int 
 
     The sound column counts the candidates of the ranges the sound MSD filter
     leaves, i.e. BEFORE the field path's per-candidate prefix test, which
-    rejects some of them ahead of the square test (that test needs the MSD
-    leaf's mask and does not run on ranges handed in from outside).
+    rejects some of them ahead of the square test.  prefix_test=True runs that
+    test too, per range (niceonly_ranges_ex: a mask per range handed in, on
+    the ranges the field path tests -- a niceonly fast base, k = 2): the sound
+    column's prefix_rejected counts the rejected candidates, its square_ok
+    only the kept ones -- the sound field's figures -- and both columns'
+    counts() gain a prefix_rejected entry (0 under the reference filter, where
+    no such test exists).  The default leaves every figure as it was.
     square_ok is counted on the GPU only for a niceonly fast base (k = 2,
     ranges inside the valid range -- every window is); elsewhere it reads 0
     there, while the CPU twin counts it for every base.
@@ -238,29 +261,25 @@ def survey_niceonly_base(ctx: Optional[api.GpuContext], base: int, windows: int 
     per_filter = {}
     with ThreadPoolExecutor(max(1, threads)) as pool:
         for filt in ("reference", "sound"):
-            if small and per_filter:
+            prefix = prefix_test and filt == "sound"
+            if small and per_filter and not prefix_test:
                 per_filter[filt] = dataclasses.replace(per_filter["reference"], filter=filt)
                 continue
             if small:
                 ranges = list(w)
             elif msd_where == "device":
-                per_filter[filt] = _device_filter_survey(ctx, w, base, msd_floor, filt)
+                per_filter[filt] = dataclasses.replace(_device_filter_survey(ctx, w, base, msd_floor, filt, prefix),
+                                                       with_prefix=prefix_test)
                 continue
             else:
                 ranges = [x for rs in pool.map(lambda win: _msd_ranges(win, base, msd_floor, filt), w)
                           for x in rs]
-            cand = sq = 0
+            cand = sq = rej = 0
             found: List[int] = []
             for i in range(0, len(ranges), NICEONLY_BATCH):
-                part = ranges[i:i + NICEONLY_BATCH]
-                if ctx is None:
-                    c, q, lst = api.niceonly_ranges_cpu(part, base, threads=threads)
-                else:
-                    c, q, lst = ctx.niceonly_ranges(part, base)
-                cand += sum(c)
-                sq += sum(q)
-                found += [n for n, _ in lst]
+                c, q, r_, f = _niceonly_batch(ctx, ranges[i:i + NICEONLY_BATCH], base, threads, prefix)
+                cand, sq, rej, found = cand + c, sq + q, rej + r_, found + f
             per_filter[filt] = NiceonlyFilterSurvey(filt, len(ranges), sum(b - a for a, b in ranges), cand, sq,
-                                                    found)
+                                                    found, rej, prefix_test)
     return NiceonlySurveyResult(base, w, msd_floor, r.range_end - r.range_start, sum(b - a for a, b in w),
                                 per_filter["reference"], per_filter["sound"])
